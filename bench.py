@@ -12,9 +12,14 @@ frames on the GPU (info bits -> [u, A.u] -> BPSK -> AWGN -> LLR), decode them
 (up to 50 iterations with early termination) and reduce the main.py counters
 on the device.  With N GPUs (one process per GPU, launched by
 torch.distributed.run) every rank decodes its own disjoint frame range and the
-counters are summed with ONE all-reduce over RCCL (weak scaling).  After the
-timed region, one step each at --extra-snr points (default 2.0 and 3.0 dB) is
-timed and reported under "snr_points" (scope "step"), then --point-snr (default
+counters are summed with ONE all-reduce over RCCL (weak scaling).
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only that: set up,
+W warm-up steps, N timed steps, the JSON line (and --dump-outputs DIR: the last
+timed step's counters as DIR/counters.npy).  Everything below runs after the
+timed region and only with --full (or when its own option asks for it): one
+step each at --extra-snr points (--full: 2.0 and 3.0 dB) is
+timed and reported under "snr_points" (scope "step"), then --point-snr (--full:
 3.0 dB) as ONE whole config-3 point of 262,144 frames per GPU streamed in one
 run (scope "point": the streaming tail is paid once per point, as main.py pays
 it), a few steps of the physical mode (the
@@ -33,8 +38,9 @@ ranks that answered on the communicator (`ranks_seen`), never the flag.
 
 Output: ONE JSON line on rank 0 (contract in the task statement), with
 `roofline` for the whole decode (algorithmic bytes, SURVEY.md section 8d, over
-the decode kernels' HIP-event time on the decoder's stream) and `cpu_baseline`
-(the C oracle, OpenMP over all usable host cores, bounded sample).
+the decode kernels' HIP-event time on the decoder's stream, taken from the
+timed steps themselves) and, with --full, `cpu_baseline` (the C oracle, OpenMP
+over all usable host cores, bounded sample).
 """
 import argparse
 import json
@@ -51,6 +57,20 @@ sys.path.insert(0, os.path.join(ROOT, "ldpc-simulator_amd"))
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md)
 SEED = 20260213
 METRIC = "decoded codewords/s + info-bits/s at fixed (N, rate, max_iter, Eb/N0)"
+
+# Everything measured after the headline's timed steps, each a run of its own:
+# option -> (value in a plain run, value under --full).  A plain run sets up,
+# warms up, times --steps steps and prints the line.
+FULL_EXTRAS = {
+    "extra_snr": ("", "2.0,3.0"),
+    "point_snr": ("", "3.0"),
+    "cpu_seconds": (0.0, 12.0),
+    "phys_steps": (0, 4),
+    "config4_snr": ("", "1.0:0.5:4.0"),
+    "config2": (0, 1),
+    "config5": (0, 1),
+    "dropin_calls": (0, 20),
+}
 
 
 def parse():
@@ -73,53 +93,68 @@ def parse():
                     help="parity mode: per-iteration CN/VN launches even where the tile-resident decoder applies")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--snr", type=float, default=1.0, help="reference SNR axis (dB), speed=1")
-    ap.add_argument("--extra-snr", default="2.0,3.0",
-                    help="comma-separated SNR points timed for one step each after the headline ('' = none)")
-    ap.add_argument("--point-snr", default="3.0",
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything in FULL_EXTRAS at its --full default (extra and "
+                         "whole SNR points, physical mode, configs 2/4/5, drop-in calls, CPU baseline); without it "
+                         "only the extras asked for by their own options run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (float64): "
+                         "counters.npy, the step's [1, 7] Monte-Carlo counters after the all-reduce")
+    ap.add_argument("--extra-snr", default=None,
+                    help="comma-separated SNR points timed for one step each after the headline ('' = none; "
+                         "--full: 2.0,3.0)")
+    ap.add_argument("--point-snr", default=None,
                     help="comma-separated SNR points streamed as ONE whole point of --point-frames frames per GPU "
                          "(config 3's per-SNR batch; the streaming tail is paid once per point, as in main.py's "
-                         "per-point loop) and reported under 'snr_points' with scope 'point' ('' = none)")
+                         "per-point loop) and reported under 'snr_points' with scope 'point' ('' = none; "
+                         "--full: 3.0)")
     ap.add_argument("--point-frames", type=int, default=262144, help="frames per GPU of a whole --point-snr point")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline sample budget (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=None,
+                    help="CPU-baseline sample budget (0 = skip; --full: 12)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every usable host core (usable_cores())")
     ap.add_argument("--mode", choices=("parity", "physical"), default="parity",
                     help="parity: the reference's fp64 decoder on H_std (headline); physical: "
                          "SURVEY §8 f4, standard SPA on the sparse graph, fp32, LDS-resident")
     ap.add_argument("--phys-hbm", action="store_true",
                     help="physical mode: HBM-resident state even when a frame fits in LDS")
-    ap.add_argument("--phys-steps", type=int, default=4,
+    ap.add_argument("--phys-steps", type=int, default=None,
                     help="parity mode: timed physical-mode steps reported under 'physical' after the "
-                         "headline (0 = none); not the reference's arithmetic (SURVEY 8 f4)")
+                         "headline (0 = none; --full: 4); not the reference's arithmetic (SURVEY 8 f4)")
     ap.add_argument("--phys-waterfall-snr", type=float, default=-2.5,
                     help="parity mode: a second physical-mode point in the waterfall, where the decoder "
                          "iterates (reported under physical.waterfall; NaN = none)")
     ap.add_argument("--phys-frames", type=int, default=262144,
                     help="frames per physical-mode step (config 3's batch; 65,536 measured 2.7 %% slower: host syncs)")
-    ap.add_argument("--config4-snr", default="1.0:0.5:4.0",
+    ap.add_argument("--config4-snr", default=None,
                     help="parity mode: BASELINE config 4's Eb/N0 sweep (start:step:end, main.py's grid) on "
-                         "--config4-code, reported under 'config4' ('' = none)")
+                         "--config4-code, reported under 'config4' ('' = none; --full: 1.0:0.5:4.0)")
     ap.add_argument("--config4-code", default="wimax_2304_0.75A")
     ap.add_argument("--config4-frames", type=int, default=32768,
                     help="frames per GPU per config-4 point (one GPU's shard of 262,144 over 8 GPUs)")
     ap.add_argument("--config4-slots", type=int, default=2048,
                     help="streaming slots of the config-4 decoder (256 CUs x one 8-frame tile8 workgroup)")
-    ap.add_argument("--config2", type=int, default=1,
+    ap.add_argument("--config2", type=int, default=None,
                     help="parity mode: BASELINE config 2 (wimax_576_0.5, T=50, 65,536 frames, 0 dB) timed for "
-                         "--config2-steps steps under 'config2' (0 = none)")
+                         "--config2-steps steps under 'config2' (0 = none; --full: 1)")
     ap.add_argument("--config2-steps", type=int, default=3)
-    ap.add_argument("--config5", type=int, default=1,
+    ap.add_argument("--config5", type=int, default=None,
                     help="parity mode: BASELINE config 5 (DVB-S2 n=64800 r1/2 profile, physical mode only: its "
-                         "H_std would have ~5e8 edges) under 'config5' (0 = none)")
+                         "H_std would have ~5e8 edges) under 'config5' (0 = none; --full: 1)")
     ap.add_argument("--config5-frames", type=int, default=8192, help="config-5 frames per GPU per step")
     ap.add_argument("--config5-waterfall-snr", type=float, default=-2.5,
                     help="a second config-5 point in the waterfall, where the 50-iteration decoder iterates "
                          "(~30 average iterations at -2.5 dB; NaN = none)")
-    ap.add_argument("--dropin-calls", type=int, default=20,
-                    help="parity mode: one-frame decode() calls timed under 'dropin' (main.py's call pattern; 0 = none)")
+    ap.add_argument("--dropin-calls", type=int, default=None,
+                    help="parity mode: one-frame decode() calls timed under 'dropin' (main.py's call pattern; "
+                         "0 = none; --full: 20)")
     ap.add_argument("--stub", action="store_true",
                     help="launcher rehearsal without a GPU: every rank only joins a gloo group and "
                          "counts the ranks (tests/test_bench_launch.py); also LDPC_BENCH_STUB=1")
-    return ap.parse_args()
+    args = ap.parse_args()
+    for name, (off, full) in FULL_EXTRAS.items():  # an option given on the command line keeps its value
+        if getattr(args, name) is None:
+            setattr(args, name, full if args.full else off)
+    return args
 
 
 def self_launch(args, argv):
@@ -788,13 +823,20 @@ def main():
     barrier(dist, local)
     t0 = time.perf_counter()
     totals = np.zeros((1, 7), np.int64)
+    last = None
     for s in range(args.steps):
-        totals += step(args.warmup + s, record=True)
+        last = step(args.warmup + s, record=True)
+        totals += last
     barrier(dist, local)
     elapsed = time.perf_counter() - t0
     dec.profile(False)
     prof = dec.profile_read()
     elapsed = max_over_ranks(dist, elapsed, local)
+    if args.dump_outputs and rank == 0 and last is not None:
+        # what the step's caller received from the last timed step: the main.py counters of its
+        # frames (frame indices, seed and sigma depend on the arguments only, so two builds compare)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "counters.npy"), last.astype(np.float64))
 
     # extra SNR points (one step each, after the headline's timed region), on
     # the streaming schedule: there frames stop at very different iterations,

@@ -21,7 +21,9 @@ for p in (PKG_DIR, ORACLE_DIR):
 LLR_RTOL = 1e-5
 LLR_ATOL = 1e-9
 
-GOLDEN_SETS = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "*.npz")))
+# a set is <name>.npz, or <name>.part<i>.npz files of consecutive frames where
+# one file would pass the size limit for a committed file (gen_golden.py save_set)
+GOLDEN_SETS = sorted({os.path.basename(p)[:-4].split(".part")[0] for p in glob.glob(os.path.join(GOLDEN, "*.npz"))})
 
 
 def pytest_configure(config):
@@ -49,8 +51,15 @@ def hstd_for(name):
 
 
 def load_golden(set_name):
-    g = np.load(os.path.join(GOLDEN, f"{set_name}.npz"), allow_pickle=False)
-    return {k: g[k] for k in g.files}
+    whole = os.path.join(GOLDEN, f"{set_name}.npz")
+    if os.path.exists(whole):
+        g = np.load(whole, allow_pickle=False)
+        return {k: g[k] for k in g.files}
+    paths = glob.glob(os.path.join(GOLDEN, f"{set_name}.part*.npz"))
+    parts = [np.load(p, allow_pickle=False) for p in sorted(paths, key=lambda p: int(p[:-4].rsplit(".part", 1)[1]))]
+    assert parts, f"no golden set {set_name}"
+    # per-frame arrays are stacked back in frame order; the set's scalars are the same in every part
+    return {k: parts[0][k] if parts[0][k].ndim == 0 else np.concatenate([p[k] for p in parts]) for k in parts[0].files}
 
 
 def assert_llr_close(actual, expected, what, slack=None):

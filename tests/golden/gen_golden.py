@@ -27,6 +27,7 @@ fingerprints of both.
 Usage:  python tests/golden/gen_golden.py [--only NAME ...]
 """
 import argparse
+import glob
 import hashlib
 import multiprocessing as mp
 import os
@@ -101,6 +102,32 @@ def load_code(name):
         out["hstd_indices"] = hs.indices.astype(np.int32)
     np.savez_compressed(os.path.join(CODES_OUT, f"{name}.npz"), **out)
     return edd
+
+
+MAX_FILE_BYTES = 1000000  # a committed file stays under 1 MiB
+
+
+def save_set(set_name, rec, out_dir=HERE):
+    """<set>.npz, or <set>.part<i>.npz files of consecutive frames (the fewest
+    equal parts that each fit MAX_FILE_BYTES); tests/conftest.py load_golden
+    stacks the per-frame arrays back in order.  Scalars go into every part."""
+    frames = max(v.shape[0] for v in rec.values() if np.ndim(v) > 0)
+    for pat in (f"{set_name}.npz", f"{set_name}.part*.npz"):
+        for f in glob.glob(os.path.join(out_dir, pat)):
+            os.remove(f)
+    for nparts in range(1, frames + 1):
+        per = -(-frames // nparts)
+        assert nparts == 1 or all(np.ndim(v) == 0 or v.shape[0] == frames for v in rec.values())
+        names = [os.path.join(out_dir, f"{set_name}.npz" if nparts == 1 else f"{set_name}.part{i}.npz")
+                 for i in range(nparts)]
+        for i, f in enumerate(names):
+            np.savez_compressed(f, **{k: v if np.ndim(v) == 0 else np.asarray(v)[i * per:(i + 1) * per]
+                                      for k, v in rec.items()})
+        if all(os.path.getsize(f) <= MAX_FILE_BYTES for f in names):
+            return names
+        for f in names:
+            os.remove(f)
+    raise ValueError(f"{set_name}: one frame does not fit {MAX_FILE_BYTES} bytes")
 
 
 def _capture_decode(dec, db):
@@ -203,7 +230,7 @@ def run_set(pool, set_name, code, T, snrs, frames, nllr, base_seed, overrides=No
     )
     rec["E"] = E_all if code == "BCH_7_4_1_strip" else E_all[:, ::E_STRIDE].copy()
     del full_e
-    np.savez_compressed(os.path.join(HERE, f"{set_name}.npz"), **rec)
+    save_set(set_name, rec)
     print(f"[{set_name}] {len(jobs)} frames in {time.time()-t0:.1f}s; "
           f"ok={rec['ok'].mean():.3f} conv>=0:{(rec['conv']>=0).sum()}", flush=True)
 

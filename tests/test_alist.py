@@ -6,13 +6,13 @@ import pytest
 from scipy import sparse
 
 from ldpc_amd import alist
-from conftest import load_code_npz
+from conftest import GOLDEN, load_code_npz
 
-REF_DB = "/root/reference/Channel_Codes_Database"
+REF_DB = os.path.join(GOLDEN, "reference_db")  # the reference database's own ALIST files, stored copies
 NAMES = {
     "BCH_7_4_1_strip": "BCH_7_4_1_strip.alist.txt",
-    "wimax_576_0.5": "Wimax LDPC Codes/wimax_576_0.5.alist.txt",
-    "wimax_2304_0.5": "Wimax LDPC Codes/wimax_2304_0.5.alist.txt",
+    "wimax_576_0.5": "wimax_576_0.5.alist.txt",
+    "wimax_2304_0.5": "wimax_2304_0.5.alist.txt",
 }
 
 
@@ -32,12 +32,9 @@ def test_roundtrip_committed_codes(name, tmp_path):
 
 @pytest.mark.parametrize("name", sorted(NAMES))
 def test_reads_reference_files_like_reference(name):
-    """When the reference tree is present (build container), parse its ALIST
-    files and compare with the CSR the reference reader produced (golden)."""
-    path = os.path.join(REF_DB, NAMES[name])
-    if not os.path.exists(path):
-        pytest.skip("reference database not present (GPU box)")
-    H = alist.read_parity_check_matrix(path)
+    """Parse the reference database's ALIST files (tests/golden/reference_db)
+    and compare with the CSR the reference reader produced (golden)."""
+    H = alist.read_parity_check_matrix(os.path.join(REF_DB, NAMES[name]))
     ref = _H(load_code_npz(name))
     np.testing.assert_array_equal(H.indptr, ref.indptr)
     np.testing.assert_array_equal(H.indices, ref.indices)

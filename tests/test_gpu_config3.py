@@ -96,7 +96,7 @@ def test_bench_3db_point_shape(gpu_available):
     H = hstd_for(code)
     g = Graph.cached(H)
     PF, slots, T = 262144, STEP // 4, 50
-    base = (1 + 3 + 2) * STEP  # bench.py defaults: warmup 1, steps 3, two extra points
+    base = (1 + 3 + 2) * STEP  # bench.py --full defaults: warmup 1, steps 3, two extra points
     sg = oracle.sigma_for_snr(3.0)
     dec = Decoder(g, slots)
     dec.profile(True)

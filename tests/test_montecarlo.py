@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import oracle
-from conftest import hstd_for
+from conftest import GOLDEN, hstd_for
 from ldpc_amd import montecarlo as mc
 from ldpc_amd.results import SimulationResult
 
@@ -156,10 +156,9 @@ def test_results_json_csv_roundtrip(tmp_path):
 
 
 def test_reads_reference_results_file():
-    """Our loader reads the reference's committed results.json (schema parity)."""
-    path = "/root/reference/python_ldpc_app/results.json"
-    if not os.path.exists(path):
-        pytest.skip("reference tree not present (GPU box)")
+    """Our loader reads the reference's committed results.json (schema parity;
+    tests/golden/reference_results.json is a stored copy of that file)."""
+    path = os.path.join(GOLDEN, "reference_results.json")
     r = SimulationResult.from_json(path)
     raw = json.load(open(path))
     assert len(r.snr_points) == len(raw["snr_points"])

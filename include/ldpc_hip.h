@@ -113,6 +113,11 @@ const char *ldpc_tile_kernel_name(const ldpc_graph *g);
 /* Physical-mode kernel for this (sparse) graph: "phys_reg_kernel" / "phys_kernel"
  * (state in LDS) or "phys_cn_tile_kernel" (state in HBM). */
 const char *ldpc_phys_kernel_name(const ldpc_graph *g, uint32_t flags);
+/* The same for a check-node rule and schedule (LDPC_CN_*, LDPC_SCHED_*, below):
+ * the flooding names above whatever the rule (the rule is a template parameter
+ * of those kernels), "phys_layered_kernel" for the layered schedule, "" for a
+ * combination ldpc_phys_decode_ex rejects. */
+const char *ldpc_phys_kernel_name_ex(const ldpc_graph *g, uint32_t flags, int32_t cn_rule, int32_t schedule);
 int ldpc_graph_info(const ldpc_graph *g, int32_t *m, int32_t *n, int64_t *nnz,
                     int32_t *max_row_deg, int32_t *max_col_deg);
 
@@ -217,6 +222,51 @@ int ldpc_phys_decode(const ldpc_graph *g, int32_t batch, const double *llr, int3
 int ldpc_phys_mc_run(ldpc_decoder *d_std, const ldpc_graph *g_phys, uint64_t seed, int32_t n_points,
                      const double *sigmas, int64_t frames_per_point, int64_t frame0, int32_t max_iter,
                      uint32_t flags, int64_t *counters_out, void *stream);
+
+/* Check-node rules and schedules of physical mode (ldpc_phys_decode_ex,
+ * ldpc_phys_mc_run_ex).  All arithmetic is fp32, every operation rounds once:
+ *   Q_e = L[c_e] - E_e over a row's edges in CSR order, s_e = (Q_e < 0);
+ *   LDPC_CN_SPA  the phi-domain sum-product rule above;
+ *   LDPC_CN_NMS  R_e = +-alpha * min over the other edges of |Q|   (normalized min-sum)
+ *   LDPC_CN_OMS  R_e = +-max(min over the other edges of |Q| - beta, 0)   (offset min-sum)
+ *                sign: negative iff the parity of the other edges' s is odd;
+ *                a graph with a row of fewer than 2 edges is LDPC_EINVAL;
+ *   LDPC_SCHED_FLOODING  every row from the same L and E, then L = Lambda + sum E
+ *                        over a column's edges, rows ascending;
+ *   LDPC_SCHED_LAYERED   layers in order (ldpc_layers_build), per row
+ *                        L[c_e] = Q_e + R_e, E_e = R_e: later layers of an
+ *                        iteration see the earlier ones' posteriors.
+ * Both stop after the first full iteration whose b = (L < 0) has H b = 0.
+ * Supported: SPA flooding (= ldpc_phys_decode, the default); NMS / OMS flooding
+ * on the LDS and the HBM path (bit-identical); NMS / OMS layered on the LDS
+ * path (E and L in LDS: ldpc_phys_lds_bytes minus 4 n bytes <= ~159 KB).
+ * SPA layered is LDPC_EINVAL; layered with LDPC_F_PHYS_HBM or on a graph too
+ * large for LDS is LDPC_ERANGE.  The min-sum results equal a CPU restatement
+ * of these rules bit for bit (tests/minsum_ref.py). */
+#define LDPC_CN_SPA 0
+#define LDPC_CN_NMS 1
+#define LDPC_CN_OMS 2
+#define LDPC_SCHED_FLOODING 0
+#define LDPC_SCHED_LAYERED 1
+/* ldpc_phys_decode with a rule and a schedule.  param: alpha in (0, 1] for
+ * LDPC_CN_NMS, beta >= 0 for LDPC_CN_OMS, ignored for LDPC_CN_SPA.  With
+ * LDPC_CN_SPA and LDPC_SCHED_FLOODING it is ldpc_phys_decode. */
+int ldpc_phys_decode_ex(const ldpc_graph *g, int32_t batch, const double *llr, int32_t max_iter, uint32_t flags,
+                        int32_t cn_rule, int32_t schedule, float param, uint8_t *z_out, int32_t *conv_out,
+                        int32_t *status_out, int32_t *iters_out, float *post_out, void *stream);
+/* ldpc_phys_mc_run with a rule and a schedule (same counters). */
+int ldpc_phys_mc_run_ex(ldpc_decoder *d_std, const ldpc_graph *g_phys, uint64_t seed, int32_t n_points,
+                        const double *sigmas, int64_t frames_per_point, int64_t frame0, int32_t max_iter,
+                        uint32_t flags, int32_t cn_rule, int32_t schedule, float param, int64_t *counters_out,
+                        void *stream);
+/* The layers of the layered schedule, on the host (no device is touched):
+ * first-fit over the rows in ascending order -- a row joins the lowest-numbered
+ * layer none of whose rows shares a column with it, else it opens a new layer.
+ * layer_of_row_out [m]; *n_layers_out = layers made.  Input as
+ * ldpc_graph_create (same checks).  A graph builds its own table with this rule
+ * on its first layered decode, not at creation. */
+int ldpc_layers_build(int32_t m, int32_t n, const int32_t *row_ptr, const int32_t *col_idx,
+                      int32_t *layer_of_row_out, int32_t *n_layers_out);
 
 /* ------------------------------------------------------------ profiling
  * HIP-event timing of the decoder's own launches, on the stream they are

@@ -11,6 +11,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -19,6 +20,7 @@
 
 using ldpc::DevGraph;
 using ldpc::DevState;
+using ldpc::PhysRule;
 using ldpc::PhysTile;
 using ldpc::kTile;
 
@@ -48,6 +50,14 @@ struct ldpc_graph {
     std::vector<int> h_row_ptr, h_col_idx;
     int *d_ints = nullptr;       // one allocation for all index arrays
     uint32_t *d_apack = nullptr;  // bit-packed A (std_form graphs only)
+    int min_row_deg = 0;
+    // layer table of the layered schedule: built and uploaded on the graph's
+    // first layered decode (graph_layers), by whichever thread gets there first
+    mutable std::once_flag layers_once;
+    mutable int layers_rc = LDPC_OK;
+    mutable std::string layers_err;
+    mutable int *d_layers = nullptr;  // layer_ptr [n_layers + 1], then layer_rows [m]
+    mutable int n_layers = 0, max_layer = 0;
 };
 
 struct ldpc_decoder {
@@ -95,6 +105,9 @@ struct ldpc_decoder {
 };
 
 namespace {
+
+// LDS a physical-mode workgroup may take (a frame's state must fit)
+constexpr size_t kLdsLimit = 160 * 1024 - 1024;
 
 // scratch slots (max_row_deg x 64 doubles) per tile the tile decoders need:
 // two buffers of a row per workgroup (rare rows alternate), four for tile8's
@@ -446,34 +459,79 @@ int ldpc_device_count(void) {
 }
 
 // ------------------------------------------------------------------ graph
+namespace {
+
+// The CSR checks ldpc_graph_create and ldpc_layers_build share (`fn` names the
+// caller in the message); max_row / min_row: the largest / smallest row degree.
+int check_csr(const char *fn, int32_t m, int32_t n, const int32_t *row_ptr, const int32_t *col_idx, int *max_row,
+              int *min_row) {
+    if (m <= 0 || n <= 0 || m > n || !row_ptr || !col_idx)
+        return ldpc_fail(LDPC_EINVAL, "%s: bad shape m=%d n=%d", fn, m, n);
+    if (row_ptr[0] != 0) return ldpc_fail(LDPC_EINVAL, "%s: row_ptr[0] != 0", fn);
+    const int64_t nnz = row_ptr[m];
+    // within-tile offsets are 32-bit: e*64 must fit
+    if (nnz <= 0 || nnz > (int64_t)(INT32_MAX / kTile) || (int64_t)n > (int64_t)(INT32_MAX / kTile))
+        return ldpc_fail(LDPC_ERANGE, "%s: nnz=%lld outside 32-bit tile indexing", fn, (long long)nnz);
+    *max_row = 0;
+    *min_row = INT_MAX;
+    for (int r = 0; r < m; ++r) {
+        const int b = row_ptr[r], e = row_ptr[r + 1];
+        if (e < b) return ldpc_fail(LDPC_EINVAL, "%s: row_ptr not monotone at %d", fn, r);
+        *max_row = std::max(*max_row, e - b);
+        *min_row = std::min(*min_row, e - b);
+        for (int i = b; i < e; ++i) {
+            if (col_idx[i] < 0 || col_idx[i] >= n)
+                return ldpc_fail(LDPC_EINVAL, "%s: column %d out of range", fn, col_idx[i]);
+            if (i > b && col_idx[i] <= col_idx[i - 1])
+                return ldpc_fail(LDPC_EINVAL,
+                                 "%s: row %d columns not strictly ascending "
+                                 "(the reference's check_to_var order is required)",
+                                 fn, r);
+        }
+    }
+    return LDPC_OK;
+}
+
+// First-fit layers: rows in ascending order, each into the lowest-numbered
+// layer none of whose rows shares a column with it, else a new layer.
+// O(nnz x layers): used[l][c] = layer l already holds column c.
+int first_fit_layers(int m, int n, const int *row_ptr, const int *col_idx, int *layer_of_row) {
+    std::vector<std::vector<uint8_t>> used;
+    for (int r = 0; r < m; ++r) {
+        size_t l = 0;
+        for (; l < used.size(); ++l) {
+            bool clash = false;
+            for (int e = row_ptr[r]; e < row_ptr[r + 1] && !clash; ++e) clash = used[l][col_idx[e]] != 0;
+            if (!clash) break;
+        }
+        if (l == used.size()) used.emplace_back((size_t)n, (uint8_t)0);
+        for (int e = row_ptr[r]; e < row_ptr[r + 1]; ++e) used[l][col_idx[e]] = 1;
+        layer_of_row[r] = (int)l;
+    }
+    return (int)used.size();
+}
+
+}  // namespace
+
+int ldpc_layers_build(int32_t m, int32_t n, const int32_t *row_ptr, const int32_t *col_idx,
+                      int32_t *layer_of_row_out, int32_t *n_layers_out) {
+    int max_row = 0, min_row = 0;
+    if (int rc = check_csr("ldpc_layers_build", m, n, row_ptr, col_idx, &max_row, &min_row)) return rc;
+    if (!layer_of_row_out || !n_layers_out) return ldpc_fail(LDPC_EINVAL, "ldpc_layers_build: NULL output");
+    *n_layers_out = first_fit_layers(m, n, row_ptr, col_idx, layer_of_row_out);
+    return LDPC_OK;
+}
+
 int ldpc_graph_create(int32_t m, int32_t n, const int32_t *row_ptr, const int32_t *col_idx, int32_t device,
                       ldpc_graph **out) {
     if (!out) return ldpc_fail(LDPC_EINVAL, "ldpc_graph_create: out is NULL");
     *out = nullptr;
-    if (m <= 0 || n <= 0 || m > n || !row_ptr || !col_idx)
-        return ldpc_fail(LDPC_EINVAL, "ldpc_graph_create: bad shape m=%d n=%d", m, n);
-    if (row_ptr[0] != 0) return ldpc_fail(LDPC_EINVAL, "ldpc_graph_create: row_ptr[0] != 0");
+    int max_row = 0, min_row = 0;
+    if (int rc = check_csr("ldpc_graph_create", m, n, row_ptr, col_idx, &max_row, &min_row)) return rc;
     const int64_t nnz = row_ptr[m];
-    // within-tile offsets are 32-bit: e*64 must fit
-    if (nnz <= 0 || nnz > (int64_t)(INT32_MAX / kTile) || (int64_t)n > (int64_t)(INT32_MAX / kTile))
-        return ldpc_fail(LDPC_ERANGE, "ldpc_graph_create: nnz=%lld outside 32-bit tile indexing", (long long)nnz);
-    int max_row = 0;
-    for (int r = 0; r < m; ++r) {
-        const int b = row_ptr[r], e = row_ptr[r + 1];
-        if (e < b) return ldpc_fail(LDPC_EINVAL, "ldpc_graph_create: row_ptr not monotone at %d", r);
-        max_row = std::max(max_row, e - b);
-        for (int i = b; i < e; ++i) {
-            if (col_idx[i] < 0 || col_idx[i] >= n)
-                return ldpc_fail(LDPC_EINVAL, "ldpc_graph_create: column %d out of range", col_idx[i]);
-            if (i > b && col_idx[i] <= col_idx[i - 1])
-                return ldpc_fail(LDPC_EINVAL,
-                                 "ldpc_graph_create: row %d columns not strictly ascending "
-                                 "(the reference's check_to_var order is required)",
-                                 r);
-        }
-    }
     if (int rc = require_gpu()) return rc;
     auto *g = new ldpc_graph;
+    g->min_row_deg = min_row;
     g->h_row_ptr.assign(row_ptr, row_ptr + m + 1);
     g->h_col_idx.assign(col_idx, col_idx + nnz);
     // CSC view with rows ascending (var_to_check order; also the order scipy's
@@ -590,6 +648,7 @@ int ldpc_graph_destroy(ldpc_graph *g) {
     DeviceGuard dg(g->device);
     (void)hipFree(g->d_ints);
     (void)hipFree(g->d_apack);
+    (void)hipFree(g->d_layers);
     delete g;
     return LDPC_OK;
 }
@@ -617,6 +676,15 @@ const char *ldpc_phys_kernel_name(const ldpc_graph *g, uint32_t flags) {
     if (!g) return "";
     if (!phys_use_lds(g->dg, flags)) return "phys_cn_tile_kernel";
     return ldpc::phys_block_threads(g->dg) > 256 ? "phys_reg_kernel" : "phys_kernel";
+}
+
+const char *ldpc_phys_kernel_name_ex(const ldpc_graph *g, uint32_t flags, int32_t cn_rule, int32_t schedule) {
+    if (!g || cn_rule < LDPC_CN_SPA || cn_rule > LDPC_CN_OMS) return "";
+    if (schedule == LDPC_SCHED_FLOODING) return ldpc_phys_kernel_name(g, flags);
+    if (schedule != LDPC_SCHED_LAYERED || cn_rule == LDPC_CN_SPA || (flags & LDPC_F_PHYS_HBM) ||
+        ldpc::phys_layered_lds_bytes(g->dg) > kLdsLimit)
+        return "";
+    return "phys_layered_kernel";
 }
 
 int ldpc_graph_info(const ldpc_graph *g, int32_t *m, int32_t *n, int64_t *nnz, int32_t *max_row_deg,
@@ -1184,8 +1252,6 @@ int ldpc_rare_rows_read(ldpc_decoder *d, int64_t *out) {
 // ---------------------------------------------------------- physical mode
 namespace {
 
-constexpr size_t kLdsLimit = 160 * 1024 - 1024;
-
 int phys_grid(const DevGraph &G) {
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) {
@@ -1199,6 +1265,89 @@ int phys_grid(const DevGraph &G) {
     return cus * per_cu;
 }
 
+// the layered kernel's grid, likewise: workgroups of phys_layered_threads
+// resident per CU by LDS (E and L only) and by the 32-wave limit
+int phys_layered_grid(const DevGraph &G, const PhysRule &rule) {
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) {
+        hipDeviceProp_t p;
+        if (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) cus = p.multiProcessorCount;
+    }
+    const size_t lds = ldpc::phys_layered_lds_bytes(G) + 64;
+    const int waves = ldpc::phys_layered_threads(rule) / 64;
+    int per_cu = (int)std::min<size_t>(32 / waves, kLdsLimit / lds);
+    // LDPC_LAYERED_PER_CU (read per launch): fewer workgroups per CU than fit (A/B)
+    if (const char *e = getenv("LDPC_LAYERED_PER_CU")) per_cu = std::min(per_cu, atoi(e));
+    if (per_cu < 1) per_cu = 1;
+    return cus * per_cu;
+}
+
+// The graph's layer table on its device, built on the first call (any thread).
+int graph_layers(const ldpc_graph *g, PhysRule *rule) {
+    std::call_once(g->layers_once, [g] {
+        const DevGraph &G = g->dg;
+        std::vector<int> of_row(G.m);
+        const int nl = first_fit_layers(G.m, G.n, g->h_row_ptr.data(), g->h_col_idx.data(), of_row.data());
+        std::vector<int> tab((size_t)nl + 1 + G.m, 0);  // layer_ptr, then layer_rows (rows ascending in a layer)
+        for (int r = 0; r < G.m; ++r) tab[of_row[r] + 1]++;
+        int biggest = 0;
+        for (int l = 0; l < nl; ++l) {
+            biggest = std::max(biggest, tab[l + 1]);
+            tab[l + 1] += tab[l];
+        }
+        std::vector<int> fill(tab.begin(), tab.begin() + nl);
+        for (int r = 0; r < G.m; ++r) tab[(size_t)nl + 1 + fill[of_row[r]]++] = r;
+        int *d = nullptr;
+        hipError_t e = hipMalloc((void **)&d, sizeof(int) * tab.size());
+        if (e == hipSuccess) e = hipMemcpy(d, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            g->layers_rc = LDPC_EDEVICE;
+            g->layers_err = std::string("layer table upload failed: ") + hipGetErrorString(e);
+            return;
+        }
+        g->d_layers = d;
+        g->n_layers = nl;
+        g->max_layer = biggest;
+    });
+    if (g->layers_rc) return ldpc_fail(g->layers_rc, "%s", g->layers_err.c_str());
+    rule->layer_ptr = g->d_layers;
+    rule->layer_rows = g->d_layers + g->n_layers + 1;
+    rule->n_layers = g->n_layers;
+    rule->max_layer = g->max_layer;
+    return LDPC_OK;
+}
+
+// Validate (cn_rule, schedule, param) for graph g and fill the kernels' rule;
+// the layered schedule gets the graph's layer table (call with g's device current).
+int phys_rule(const char *fn, const ldpc_graph *g, uint32_t flags, int32_t cn_rule, int32_t schedule, float param,
+              PhysRule *rule) {
+    if (cn_rule != LDPC_CN_SPA && cn_rule != LDPC_CN_NMS && cn_rule != LDPC_CN_OMS)
+        return ldpc_fail(LDPC_EINVAL, "%s: unknown check-node rule %d", fn, cn_rule);
+    if (schedule != LDPC_SCHED_FLOODING && schedule != LDPC_SCHED_LAYERED)
+        return ldpc_fail(LDPC_EINVAL, "%s: unknown schedule %d", fn, schedule);
+    if (cn_rule == LDPC_CN_NMS && !(param > 0.0f && param <= 1.0f))
+        return ldpc_fail(LDPC_EINVAL, "%s: normalized min-sum needs alpha in (0, 1], got %g", fn, (double)param);
+    if (cn_rule == LDPC_CN_OMS && !(param >= 0.0f))
+        return ldpc_fail(LDPC_EINVAL, "%s: offset min-sum needs beta >= 0, got %g", fn, (double)param);
+    if (cn_rule == LDPC_CN_SPA && schedule == LDPC_SCHED_LAYERED)
+        return ldpc_fail(LDPC_EINVAL, "%s: the layered schedule is not implemented for the sum-product rule "
+                                      "(use LDPC_CN_NMS or LDPC_CN_OMS)", fn);
+    if (cn_rule != LDPC_CN_SPA && g->min_row_deg < 2)
+        return ldpc_fail(LDPC_EINVAL, "%s: min-sum needs every check row to have at least 2 edges (a row has %d)",
+                         fn, g->min_row_deg);
+    *rule = PhysRule{};
+    rule->cn = cn_rule;
+    rule->param = cn_rule == LDPC_CN_SPA ? 0.0f : param;
+    if (schedule == LDPC_SCHED_LAYERED) {
+        if ((flags & LDPC_F_PHYS_HBM) || ldpc::phys_layered_lds_bytes(g->dg) > kLdsLimit)
+            return ldpc_fail(LDPC_ERANGE, "%s: the layered schedule runs only with a frame's state in LDS "
+                                          "(not with LDPC_F_PHYS_HBM, nor on a graph too large for LDS)", fn);
+        return graph_layers(g, rule);
+    }
+    return LDPC_OK;
+}
+
 
 }  // namespace
 
@@ -1208,12 +1357,19 @@ namespace {
 
 int phys_decode_lds(const ldpc_graph *g, int32_t batch, const double *llr, int32_t max_iter, uint32_t flags,
                     uint8_t *z_out, int32_t *conv_out, int32_t *status_out, int32_t *iters_out, float *post_out,
-                    hipStream_t s) {
+                    hipStream_t s, const PhysRule &rule) {
     const DevGraph &G = g->dg;
     const size_t n = (size_t)G.n, B = (size_t)batch;
+    // flooding (any rule) or, with a layer table, the layered kernel
+    auto launch = [&](const double *in, uint8_t *z, int *conv, int *status, int *iters, float *post) {
+        if (rule.layer_ptr)
+            return ldpc::launch_phys_layered(G, in, nullptr, 0, batch, max_iter, z, conv, status, iters, post, nullptr,
+                                             nullptr, std::min(phys_layered_grid(G, rule), batch), s, rule);
+        return ldpc::launch_phys(G, in, nullptr, 0, batch, max_iter, z, conv, status, iters, post, nullptr, nullptr,
+                                 std::min(phys_grid(G), batch), s, rule);
+    };
     if (flags & LDPC_F_DEVICE_PTRS) {
-        HIP_TRY(ldpc::launch_phys(G, llr, nullptr, 0, batch, max_iter, z_out, conv_out, status_out, iters_out, post_out,
-                                  nullptr, nullptr, std::min(phys_grid(G), batch), s));
+        HIP_TRY(launch(llr, z_out, conv_out, status_out, iters_out, post_out));
         return LDPC_OK;
     }
     double *d_llr = nullptr;
@@ -1227,8 +1383,7 @@ int phys_decode_lds(const ldpc_graph *g, int32_t batch, const double *llr, int32
     hipError_t e = hipSuccess;
     if (!rc) {
         e = hipMemcpyAsync(d_llr, llr, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
-        if (!e) e = ldpc::launch_phys(G, d_llr, nullptr, 0, batch, max_iter, d_z, d_i, d_i + B, d_i + 2 * B, d_post, nullptr,
-                                     nullptr, std::min(phys_grid(G), batch), s);
+        if (!e) e = launch(d_llr, d_z, d_i, d_i + B, d_i + 2 * B, d_post);
         if (!e && z_out) e = hipMemcpyAsync(z_out, d_z, B * n, hipMemcpyDeviceToHost, s);
         if (!e && conv_out) e = hipMemcpyAsync(conv_out, d_i, sizeof(int) * B, hipMemcpyDeviceToHost, s);
         if (!e && status_out) e = hipMemcpyAsync(status_out, d_i + B, sizeof(int) * B, hipMemcpyDeviceToHost, s);
@@ -1253,7 +1408,7 @@ int phys_decode_lds(const ldpc_graph *g, int32_t batch, const double *llr, int32
 // most a quarter of the launched slots hold them, the finished frames counted
 // into ctr first (phys_tile.hip).
 int phys_tile_decode(ldpc_decoder *d, const DevGraph &P, int max_iter, bool from_ch, hipStream_t s,
-                     unsigned long long *ctr = nullptr) {
+                     unsigned long long *ctr = nullptr, const PhysRule &rule = PhysRule{}) {
     if (d->pactive_cap < 2 * max_iter) {
         (void)hipFree(d->pactive);
         d->pactive = nullptr;
@@ -1272,7 +1427,7 @@ int phys_tile_decode(ldpc_decoder *d, const DevGraph &P, int max_iter, bool from
     HIP_TRY(hipMemsetAsync(d->pactive, 0, sizeof(int) * 2 * max_iter, s));
     HIP_TRY(ldpc::launch_phys_tile_init(P, st, pt, from_ch, s));
     for (int it = 0; it < max_iter; ++it) {
-        HIP_TRY(timed(d, LDPC_K_PHYS_CN, s, [&] { return ldpc::launch_phys_tile_cn(P, st, pt, it, false, s); }));
+        HIP_TRY(timed(d, LDPC_K_PHYS_CN, s, [&] { return ldpc::launch_phys_tile_cn(P, st, pt, it, false, s, rule); }));
         HIP_TRY(timed(d, LDPC_K_PHYS_VN, s,
                       [&] { return ldpc::launch_phys_tile_vn(P, st, pt, it, d->pactive, max_iter, s); }));
         if (it + 1 < max_iter && (it < 4 || (it + 1) % 4 == 0)) {
@@ -1302,7 +1457,7 @@ int phys_tile_decode(ldpc_decoder *d, const DevGraph &P, int max_iter, bool from
             }
         }
     }
-    HIP_TRY(ldpc::launch_phys_tile_cn(P, st, pt, max_iter, true, s));
+    HIP_TRY(ldpc::launch_phys_tile_cn(P, st, pt, max_iter, true, s, rule));
     HIP_TRY(ldpc::launch_phys_tile_final(P, st, pt, max_iter, s));
     return LDPC_OK;
 }
@@ -1313,7 +1468,7 @@ bool phys_use_lds(const DevGraph &P, uint32_t flags) {
 
 int phys_decode_tile(const ldpc_graph *g, int32_t batch, const double *llr, int32_t max_iter, uint32_t flags,
                      uint8_t *z_out, int32_t *conv_out, int32_t *status_out, int32_t *iters_out, float *post_out,
-                     hipStream_t s) {
+                     hipStream_t s, const PhysRule &rule) {
     const DevGraph &G = g->dg;
     const bool dev_ptrs = flags & LDPC_F_DEVICE_PTRS;
     const int chunk = std::min<int>(batch, 1024);
@@ -1335,7 +1490,7 @@ int phys_decode_tile(const ldpc_graph *g, int32_t batch, const double *llr, int3
             src = d->llr_stage;
         }
         HIP_TRY(ldpc::launch_load_llr(G, st, src, s));
-        if (int rc = phys_tile_decode(d, G, max_iter, true, s)) return rc;
+        if (int rc = phys_tile_decode(d, G, max_iter, true, s, nullptr, rule)) return rc;
         uint8_t *zd = z_out ? (dev_ptrs ? z_out + (size_t)start * n : d->z_stage) : nullptr;
         float *pd = post_out ? (dev_ptrs ? post_out + (size_t)start * n : (float *)d->post_stage) : nullptr;
         HIP_TRY(ldpc::launch_phys_tile_out(G, st, phys_tile(d), zd, pd, s));
@@ -1356,39 +1511,46 @@ int phys_decode_tile(const ldpc_graph *g, int32_t batch, const double *llr, int3
 
 }  // namespace
 
-int ldpc_phys_decode(const ldpc_graph *g, int32_t batch, const double *llr, int32_t max_iter, uint32_t flags,
-                     uint8_t *z_out, int32_t *conv_out, int32_t *status_out, int32_t *iters_out, float *post_out,
-                     void *stream) {
-    if (!g) return ldpc_fail(LDPC_EINVAL, "ldpc_phys_decode: NULL graph");
+namespace {
+
+int phys_decode_any(const char *fn, const ldpc_graph *g, int32_t batch, const double *llr, int32_t max_iter,
+                    uint32_t flags, int32_t cn_rule, int32_t schedule, float param, uint8_t *z_out, int32_t *conv_out,
+                    int32_t *status_out, int32_t *iters_out, float *post_out, void *stream) {
+    if (!g) return ldpc_fail(LDPC_EINVAL, "%s: NULL graph", fn);
     if (batch < 0 || max_iter < 1 || (batch > 0 && !llr))
-        return ldpc_fail(LDPC_EINVAL, "ldpc_phys_decode: bad arguments (batch=%d max_iter=%d)", batch, max_iter);
-    if (batch == 0) return LDPC_OK;
+        return ldpc_fail(LDPC_EINVAL, "%s: bad arguments (batch=%d max_iter=%d)", fn, batch, max_iter);
     DeviceGuard dg(g->device);
+    PhysRule rule;
+    if (int rc = phys_rule(fn, g, flags, cn_rule, schedule, param, &rule)) return rc;
+    if (batch == 0) return LDPC_OK;
     hipStream_t s = (hipStream_t)stream;
-    if (phys_use_lds(g->dg, flags))
-        return phys_decode_lds(g, batch, llr, max_iter, flags, z_out, conv_out, status_out, iters_out, post_out, s);
-    return phys_decode_tile(g, batch, llr, max_iter, flags, z_out, conv_out, status_out, iters_out, post_out, s);
+    if (rule.layer_ptr || phys_use_lds(g->dg, flags))
+        return phys_decode_lds(g, batch, llr, max_iter, flags, z_out, conv_out, status_out, iters_out, post_out, s,
+                               rule);
+    return phys_decode_tile(g, batch, llr, max_iter, flags, z_out, conv_out, status_out, iters_out, post_out, s, rule);
 }
 
-int ldpc_phys_mc_run(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int32_t n_points, const double *sigmas,
-                     int64_t frames_per_point, int64_t frame0, int32_t max_iter, uint32_t flags, int64_t *counters_out,
-                     void *stream) {
-    if (!gp) return ldpc_fail(LDPC_EINVAL, "ldpc_phys_mc_run: NULL graph");
+int phys_mc_any(const char *fn, ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int32_t n_points,
+                const double *sigmas, int64_t frames_per_point, int64_t frame0, int32_t max_iter, uint32_t flags,
+                int32_t cn_rule, int32_t schedule, float param, int64_t *counters_out, void *stream) {
+    if (!gp) return ldpc_fail(LDPC_EINVAL, "%s: NULL graph", fn);
     if (!d || n_points <= 0 || !sigmas || frames_per_point < 0 || frame0 < 0 || max_iter < 1 || !counters_out)
-        return ldpc_fail(LDPC_EINVAL, "ldpc_phys_mc_run: bad arguments");
+        return ldpc_fail(LDPC_EINVAL, "%s: bad arguments", fn);
     const DevGraph &G = d->g->dg;
     const DevGraph &P = gp->dg;
     if (!G.std_form && !(G.ira && d->g == gp))
         return ldpc_fail(LDPC_EINVAL,
-                         "ldpc_phys_mc_run: the decoder's graph must be the code's H_std = [A | I_m], or the "
-                         "IRA graph itself");
+                         "%s: the decoder's graph must be the code's H_std = [A | I_m], or the "
+                         "IRA graph itself", fn);
     if (P.n != G.n || P.k != G.k)
-        return ldpc_fail(LDPC_EINVAL, "ldpc_phys_mc_run: physical graph shape %dx%d != %dx%d", P.m, P.n, G.m, G.n);
+        return ldpc_fail(LDPC_EINVAL, "%s: physical graph shape %dx%d != %dx%d", fn, P.m, P.n, G.m, G.n);
     for (int p = 0; p < n_points; ++p)
-        if (!(sigmas[p] > 0.0)) return ldpc_fail(LDPC_EINVAL, "ldpc_phys_mc_run: sigma[%d] <= 0", p);
+        if (!(sigmas[p] > 0.0)) return ldpc_fail(LDPC_EINVAL, "%s: sigma[%d] <= 0", fn, p);
     DeviceGuard dg(d->g->device);
+    PhysRule rule;
+    if (int rc = phys_rule(fn, gp, flags, cn_rule, schedule, param, &rule)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const bool lds = phys_use_lds(P, flags);
+    const bool lds = rule.layer_ptr || phys_use_lds(P, flags);
     if (!lds)
         if (int rc = ensure_phys_tile(d, P)) return rc;
     if (int rc = ensure_pbits(d, G)) return rc;
@@ -1417,11 +1579,15 @@ int ldpc_phys_mc_run(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int32
             }));
             if (lds) {
                 HIP_TRY(timed(d, LDPC_K_PHYS, s, [&] {
+                    if (rule.layer_ptr)
+                        return ldpc::launch_phys_layered(P, nullptr, rows, 2, cnt, max_iter, nullptr, nullptr, nullptr,
+                                                         nullptr, nullptr, st.ubits, ctr,
+                                                         std::min(phys_layered_grid(P, rule), cnt), s, rule);
                     return ldpc::launch_phys(P, nullptr, rows, 2, cnt, max_iter, nullptr, nullptr, nullptr, nullptr,
-                                             nullptr, st.ubits, ctr, std::min(phys_grid(P), cnt), s);
+                                             nullptr, st.ubits, ctr, std::min(phys_grid(P), cnt), s, rule);
                 }));
             } else {
-                if (int rc = phys_tile_decode(d, P, max_iter, false, s, ctr)) return rc;
+                if (int rc = phys_tile_decode(d, P, max_iter, false, s, ctr, rule)) return rc;
                 HIP_TRY(timed(d, LDPC_K_COUNT, s,
                               [&] { return ldpc::launch_phys_tile_count(P, st, phys_tile(d), ctr, s); }));
             }
@@ -1432,6 +1598,36 @@ int ldpc_phys_mc_run(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int32
     HIP_TRY(hipStreamSynchronize(s));
     for (int i = 0; i < need; ++i) counters_out[i] = (int64_t)h[i];
     return LDPC_OK;
+}
+
+}  // namespace
+
+int ldpc_phys_decode(const ldpc_graph *g, int32_t batch, const double *llr, int32_t max_iter, uint32_t flags,
+                     uint8_t *z_out, int32_t *conv_out, int32_t *status_out, int32_t *iters_out, float *post_out,
+                     void *stream) {
+    return phys_decode_any("ldpc_phys_decode", g, batch, llr, max_iter, flags, LDPC_CN_SPA, LDPC_SCHED_FLOODING, 0.0f,
+                           z_out, conv_out, status_out, iters_out, post_out, stream);
+}
+
+int ldpc_phys_decode_ex(const ldpc_graph *g, int32_t batch, const double *llr, int32_t max_iter, uint32_t flags,
+                        int32_t cn_rule, int32_t schedule, float param, uint8_t *z_out, int32_t *conv_out,
+                        int32_t *status_out, int32_t *iters_out, float *post_out, void *stream) {
+    return phys_decode_any("ldpc_phys_decode_ex", g, batch, llr, max_iter, flags, cn_rule, schedule, param, z_out,
+                           conv_out, status_out, iters_out, post_out, stream);
+}
+
+int ldpc_phys_mc_run(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int32_t n_points, const double *sigmas,
+                     int64_t frames_per_point, int64_t frame0, int32_t max_iter, uint32_t flags, int64_t *counters_out,
+                     void *stream) {
+    return phys_mc_any("ldpc_phys_mc_run", d, gp, seed, n_points, sigmas, frames_per_point, frame0, max_iter, flags,
+                       LDPC_CN_SPA, LDPC_SCHED_FLOODING, 0.0f, counters_out, stream);
+}
+
+int ldpc_phys_mc_run_ex(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int32_t n_points, const double *sigmas,
+                        int64_t frames_per_point, int64_t frame0, int32_t max_iter, uint32_t flags, int32_t cn_rule,
+                        int32_t schedule, float param, int64_t *counters_out, void *stream) {
+    return phys_mc_any("ldpc_phys_mc_run_ex", d, gp, seed, n_points, sigmas, frames_per_point, frame0, max_iter, flags,
+                       cn_rule, schedule, param, counters_out, stream);
 }
 
 // -------------------------------------------------------------- profiling

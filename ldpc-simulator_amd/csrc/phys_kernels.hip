@@ -14,6 +14,10 @@
 //   sign   = prod_{c' != c} sign(M[r,c']),   M[r,c] = L[c] - E[r,c]
 // Variable update: L[c] = Lambda[c] + sum_r E[r,c].  Flooding schedule; early
 // termination when H b = 0 with b = (L < 0); at most max_iter iterations.
+// The check rule is a template parameter: kCnNms / kCnOms replace the phi rule
+// by normalized / offset min-sum (E = sign * scale(min over the other edges of
+// |M|), phys_common.h) -- no transcendental, bit-exact against a CPU
+// restatement.  The layered schedule is phys_layered.hip.
 //
 // One workgroup (256 threads) per frame, frames grid-strided; LDS holds
 // E[nnz], L[n], Lambda[n] in fp32 (<= 42 KB for the WiMAX 2304 codes: three
@@ -24,102 +28,16 @@
 #include <cstdint>
 #include <cstdlib>
 
+#include "phys_common.h"
 #include "phys_math.h"
 #include "spa_device.h"
 
 namespace ldpc {
 namespace {
 
-struct PhysArgs {
-    DevGraph g;               // H[:, perm] (sparse)
-    const double *llr;        // [count][n] (layout 0) or ch tile layout (layout 1)
-    const float *lam;         // layout 2: [count][n] fp32 Lambda (on-device frames, frame_kernels.hip)
-    int layout;               // 0: row per frame; 1: [tile][n][64]; 2: lam
-    int count;
-    int max_iter;
-    uint8_t *z_out;           // [count][n] or null: z = (bit estimate) ^ 1
-    int *conv_out;            // [count] or null
-    int *status_out;          // [count] or null
-    int *iters_out;           // [count] or null
-    float *post_out;          // [count][n] or null
-    const uint32_t *ubits;    // MC: info bits [tile][kw][64] (layout 1), else null
-    unsigned long long *ctr;  // MC: counters [7] or null
-};
-
-// Frame f into LDS: Lambda = -channel LLR, L = Lambda, E = 0.
-__device__ __forceinline__ void frame_load(const PhysArgs &a, int f, float *E, float *L, float *Lam, int tid,
-                                           int nt) {
-    const DevGraph &g = a.g;
-    for (int j = tid; j < g.n; j += nt) {
-        if (a.layout == 2) {
-            Lam[j] = a.lam[(size_t)f * g.n + j];  // contiguous per frame
-        } else {
-            const double ch = a.layout == 0 ? a.llr[(size_t)f * g.n + j]
-                                            : a.llr[((size_t)(f >> 6) * g.n + j) * kTile + (f & 63)];
-            Lam[j] = -(float)ch;
-        }
-        L[j] = Lam[j];
-    }
-    for (int e = tid; e < g.nnz; e += nt) E[e] = 0.0f;
-}
-
-// Monte-Carlo counters of the frames one workgroup decodes (thread 0's
-// registers), added to the device counters once, when the workgroup is done:
-// one atomic per counter per frame on the same 7 addresses serialised every
-// frame of a launch in L2.
-struct FrameCounts {
-    unsigned long long v[7] = {0, 0, 0, 0, 0, 0, 0};
-    __device__ __forceinline__ void flush(unsigned long long *ctr) const {
-        if (!ctr) return;
-#pragma unroll
-        for (int i = 0; i < 7; ++i)
-            if (v[i]) atomicAdd(&ctr[i], v[i]);
-    }
-};
-
-// Outputs and Monte-Carlo counters of frame f (conv = -1: not converged).
-__device__ __forceinline__ void frame_finish(const PhysArgs &a, int f, int conv, const float *L, int *s_err,
-                                             int tid, int nt, FrameCounts &fc) {
-    const DevGraph &g = a.g;
-    const int iters = conv >= 0 ? conv + 1 : a.max_iter;
-    for (int j = tid; j < g.n; j += nt) {
-        const bool bit = L[j] < 0.0f;
-        if (a.z_out) a.z_out[(size_t)f * g.n + j] = bit ? 0 : 1;
-        if (a.post_out) a.post_out[(size_t)f * g.n + j] = L[j];
-    }
-    if (tid == 0) {
-        if (a.conv_out) a.conv_out[f] = conv;
-        if (a.status_out) a.status_out[f] = conv >= 0 ? 0 : 1;
-        if (a.iters_out) a.iters_out[f] = iters;
-        *s_err = 0;
-    }
-    if (a.ctr) {
-        __syncthreads();
-        if (conv < 0) {  // BER counts failed frames only (main.py:130-138)
-            const int kw = (g.k + 31) >> 5;
-            int my = 0;
-            for (int j = tid; j < g.k; j += nt) {
-                const uint32_t w = a.ubits[((size_t)(f >> 6) * kw + (j >> 5)) * kTile + (f & 63)];
-                my += (((w >> (j & 31)) & 1u) != (L[j] < 0.0f ? 1u : 0u)) ? 1 : 0;
-            }
-            atomicAdd(s_err, my);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            fc.v[0] += 1ull;
-            if (conv < 0) {
-                fc.v[1] += 1ull;
-                fc.v[2] += (unsigned long long)*s_err;
-            } else {
-                fc.v[3] += (unsigned long long)conv;
-                fc.v[4] += 1ull;
-            }
-            fc.v[6] += (unsigned long long)iters;
-        }
-    }
-    __syncthreads();  // LDS reused by the next frame
-}
-
+// CN: the check rule (kCnSpa: phi domain, above; kCnNms / kCnOms: min-sum,
+// first sweep for the two smallest |M| and the sign parity, second to write).
+template <int CN>
 __global__ __launch_bounds__(256) void phys_kernel(PhysArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const DevGraph &g = a.g;
@@ -137,17 +55,32 @@ __global__ __launch_bounds__(256) void phys_kernel(PhysArgs a) {
             // --- check nodes
             for (int r = tid; r < g.m; r += nt) {
                 const int b = g.row_ptr[r], e1 = g.row_ptr[r + 1];
-                float S = 0.0f;
-                unsigned neg = 0u;
-                for (int e = b; e < e1; ++e) {
-                    const float M = L[g.col_idx[e]] - E[e];
-                    S += phi(fabsf(M));
-                    neg ^= (M < 0.0f) ? 1u : 0u;
-                }
-                for (int e = b; e < e1; ++e) {
-                    const float M = L[g.col_idx[e]] - E[e];
-                    const float mag = phi(fmaxf(S - phi(fabsf(M)), 0.0f));
-                    E[e] = ((neg ^ ((M < 0.0f) ? 1u : 0u)) != 0u) ? -mag : mag;
+                if constexpr (CN == kCnSpa) {
+                    float S = 0.0f;
+                    unsigned neg = 0u;
+                    for (int e = b; e < e1; ++e) {
+                        const float M = L[g.col_idx[e]] - E[e];
+                        S += phi(fabsf(M));
+                        neg ^= (M < 0.0f) ? 1u : 0u;
+                    }
+                    for (int e = b; e < e1; ++e) {
+                        const float M = L[g.col_idx[e]] - E[e];
+                        const float mag = phi(fmaxf(S - phi(fabsf(M)), 0.0f));
+                        E[e] = ((neg ^ ((M < 0.0f) ? 1u : 0u)) != 0u) ? -mag : mag;
+                    }
+                } else {
+                    MinPair mp;
+                    unsigned neg = 0u;
+                    for (int e = b; e < e1; ++e) {
+                        const float M = L[g.col_idx[e]] - E[e];
+                        mp.add(fabsf(M), e);
+                        neg ^= (M < 0.0f) ? 1u : 0u;
+                    }
+                    for (int e = b; e < e1; ++e) {
+                        const float M = L[g.col_idx[e]] - E[e];
+                        const float mag = ms_scale<CN>(mp.other(e), a.param);
+                        E[e] = ((neg ^ ((M < 0.0f) ? 1u : 0u)) != 0u) ? -mag : mag;
+                    }
                 }
             }
             __syncthreads();
@@ -181,7 +114,7 @@ __global__ __launch_bounds__(256) void phys_kernel(PhysArgs a) {
 // frame: no index loads in the iteration loop), and phi(|M|) kept in registers
 // between the two sweeps of a row (phys_cn_tile does the same).  Identical
 // operations in identical order as phys_kernel: bit-identical results.
-template <int NT, int RPT, int RDEG, int CPT, int CDEG, int WPS>
+template <int CN, int NT, int RPT, int RDEG, int CPT, int CDEG, int WPS>
 __global__ __launch_bounds__(NT, WPS) void phys_reg_kernel(PhysArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const DevGraph &g = a.g;
@@ -231,24 +164,48 @@ __global__ __launch_bounds__(NT, WPS) void phys_reg_kernel(PhysArgs a) {
 #pragma unroll
             for (int k = 0; k < RPT; ++k) {
                 if (rdeg[k] == 0) continue;
-                float ph[RDEG];
-                uint32_t sg = 0u;
-                float S = 0.0f;
+                if constexpr (CN == kCnSpa) {
+                    float ph[RDEG];
+                    uint32_t sg = 0u;
+                    float S = 0.0f;
 #pragma unroll
-                for (int i = 0; i < RDEG; ++i) {
-                    if (i < rdeg[k]) {
-                        const float M = L[col(k, i)] - E[rbeg[k] + i];
-                        ph[i] = phi(fabsf(M));
-                        S += ph[i];
-                        sg |= (M < 0.0f ? 1u : 0u) << i;
+                    for (int i = 0; i < RDEG; ++i) {
+                        if (i < rdeg[k]) {
+                            const float M = L[col(k, i)] - E[rbeg[k] + i];
+                            ph[i] = phi(fabsf(M));
+                            S += ph[i];
+                            sg |= (M < 0.0f ? 1u : 0u) << i;
+                        }
                     }
-                }
-                const uint32_t neg = __popc(sg) & 1u;
+                    const uint32_t neg = __popc(sg) & 1u;
 #pragma unroll
-                for (int i = 0; i < RDEG; ++i) {
-                    if (i < rdeg[k]) {
-                        const float mag = phi(fmaxf(S - ph[i], 0.0f));
-                        E[rbeg[k] + i] = ((neg ^ (sg >> i)) & 1u) ? -mag : mag;
+                    for (int i = 0; i < RDEG; ++i) {
+                        if (i < rdeg[k]) {
+                            const float mag = phi(fmaxf(S - ph[i], 0.0f));
+                            E[rbeg[k] + i] = ((neg ^ (sg >> i)) & 1u) ? -mag : mag;
+                        }
+                    }
+                } else {
+                    // the row's signs in a word, the argmin as an index: the
+                    // second sweep needs no M
+                    MinPair mp;
+                    uint32_t sg = 0u;
+#pragma unroll
+                    for (int i = 0; i < RDEG; ++i) {
+                        if (i < rdeg[k]) {
+                            const float M = L[col(k, i)] - E[rbeg[k] + i];
+                            mp.add(fabsf(M), i);
+                            sg |= (M < 0.0f ? 1u : 0u) << i;
+                        }
+                    }
+                    const uint32_t neg = __popc(sg) & 1u;
+                    const float m1 = ms_scale<CN>(mp.min1, a.param), m2 = ms_scale<CN>(mp.min2, a.param);
+#pragma unroll
+                    for (int i = 0; i < RDEG; ++i) {
+                        if (i < rdeg[k]) {
+                            const float mag = i == mp.arg ? m2 : m1;
+                            E[rbeg[k] + i] = ((neg ^ (sg >> i)) & 1u) ? -mag : mag;
+                        }
                     }
                 }
             }
@@ -324,10 +281,38 @@ int reg_shape(const DevGraph &g) {
 
 int phys_block_threads(const DevGraph &g) { return reg_shape(g) >= 0 ? kRegNT : 256; }
 
+namespace {
+
+template <int CN>
+void launch_phys_rule(const PhysArgs &a, int grid, size_t lds, int wps, hipStream_t s) {
+    // the 4-wave A/B variants exist for the SPA rule only
+    const bool w6 = wps == 6 || CN != kCnSpa;
+    switch (reg_shape(a.g)) {
+    case 0: phys_reg_kernel<CN, kRegNT, 1, 8, 1, 8, 6><<<grid, kRegNT, lds, s>>>(a); break;
+    case 1: phys_reg_kernel<CN, kRegNT, 1, 8, 2, 8, 6><<<grid, kRegNT, lds, s>>>(a); break;
+    case 2:
+        if (w6) phys_reg_kernel<CN, kRegNT, 2, 8, 3, 8, 6><<<grid, kRegNT, lds, s>>>(a);
+        else if constexpr (CN == kCnSpa) phys_reg_kernel<CN, kRegNT, 2, 8, 3, 8, 4><<<grid, kRegNT, lds, s>>>(a);
+        break;
+    case 3:
+        if (w6) phys_reg_kernel<CN, kRegNT, 2, 16, 5, 8, 6><<<grid, kRegNT, lds, s>>>(a);
+        else if constexpr (CN == kCnSpa) phys_reg_kernel<CN, kRegNT, 2, 16, 5, 8, 4><<<grid, kRegNT, lds, s>>>(a);
+        break;
+    case 4:
+        if (w6) phys_reg_kernel<CN, kRegNT, 3, 8, 5, 8, 6><<<grid, kRegNT, lds, s>>>(a);
+        else if constexpr (CN == kCnSpa) phys_reg_kernel<CN, kRegNT, 3, 8, 5, 8, 4><<<grid, kRegNT, lds, s>>>(a);
+        break;
+    default: phys_kernel<CN><<<grid, 256, lds, s>>>(a);
+    }
+}
+
+}  // namespace
+
 hipError_t launch_phys(const DevGraph &g, const double *llr, const float *lam, int layout, int count, int max_iter,
                        uint8_t *z, int *conv, int *status, int *iters, float *post, const uint32_t *ubits,
-                       unsigned long long *ctr, int grid, hipStream_t s) {
-    PhysArgs a{g, llr, lam, layout, count, max_iter, z, conv, status, iters, post, ubits, ctr};
+                       unsigned long long *ctr, int grid, hipStream_t s, const PhysRule &rule) {
+    PhysArgs a{g, llr, lam, layout, count, max_iter, z, conv, status, iters, post, ubits, ctr, rule.param,
+               nullptr, nullptr, 0};
     const size_t lds = phys_lds_bytes(g);
     if (count <= 0) return hipSuccess;
     // min waves per SIMD of the large shapes: 6 = three 8-wave frames per CU (the
@@ -337,22 +322,11 @@ hipError_t launch_phys(const DevGraph &g, const double *llr, const float *lam, i
         const char *e = getenv("LDPC_PHYS_REG_WPS");
         return e ? atoi(e) : 6;
     }();
-    switch (reg_shape(g)) {
-    case 0: phys_reg_kernel<kRegNT, 1, 8, 1, 8, 6><<<grid, kRegNT, lds, s>>>(a); break;
-    case 1: phys_reg_kernel<kRegNT, 1, 8, 2, 8, 6><<<grid, kRegNT, lds, s>>>(a); break;
-    case 2:
-        if (wps == 6) phys_reg_kernel<kRegNT, 2, 8, 3, 8, 6><<<grid, kRegNT, lds, s>>>(a);
-        else phys_reg_kernel<kRegNT, 2, 8, 3, 8, 4><<<grid, kRegNT, lds, s>>>(a);
-        break;
-    case 3:
-        if (wps == 6) phys_reg_kernel<kRegNT, 2, 16, 5, 8, 6><<<grid, kRegNT, lds, s>>>(a);
-        else phys_reg_kernel<kRegNT, 2, 16, 5, 8, 4><<<grid, kRegNT, lds, s>>>(a);
-        break;
-    case 4:
-        if (wps == 6) phys_reg_kernel<kRegNT, 3, 8, 5, 8, 6><<<grid, kRegNT, lds, s>>>(a);
-        else phys_reg_kernel<kRegNT, 3, 8, 5, 8, 4><<<grid, kRegNT, lds, s>>>(a);
-        break;
-    default: phys_kernel<<<grid, 256, lds, s>>>(a);
+    switch (rule.cn) {
+    case kCnSpa: launch_phys_rule<kCnSpa>(a, grid, lds, wps, s); break;
+    case kCnNms: launch_phys_rule<kCnNms>(a, grid, lds, wps, s); break;
+    case kCnOms: launch_phys_rule<kCnOms>(a, grid, lds, wps, s); break;
+    default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }

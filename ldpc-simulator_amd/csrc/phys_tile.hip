@@ -34,6 +34,7 @@
 
 #include <cstdint>
 
+#include "phys_common.h"
 #include "phys_math.h"
 #include "spa_device.h"
 
@@ -93,10 +94,39 @@ __global__ void phys_tile_init_kernel(DevGraph g, DevState st, PhysTile pt, int 
 // unused on iteration 0, for a stopped frame or in the syndrome-only sweep):
 // phi(|M|) and the signs in registers, E_new = sign * phi(S - phi(|M_i|)).
 // Returns the row parity of the hard decisions (L < 0).
-template <int kDeg>
+// CN = kCnNms / kCnOms: the min-sum rule instead (the two smallest |M| and the
+// argmin in registers; param = alpha / beta).
+template <int kDeg, int CN>
 __device__ __forceinline__ uint32_t phys_row(float *__restrict__ Et, int beg, int deg, const float (&Lc)[kDeg],
-                                             const float (&Eo)[kDeg], bool first, bool live, bool syn_only) {
+                                             const float (&Eo)[kDeg], bool first, bool live, bool syn_only,
+                                             float param) {
     uint32_t hp = 0u, sg = 0u;
+    if constexpr (CN != kCnSpa) {
+        MinPair mp;
+#pragma unroll
+        for (int i = 0; i < kDeg; ++i) {
+            if (i < deg) {
+                hp ^= Lc[i] < 0.0f ? 1u : 0u;
+                if (!syn_only) {
+                    const float M = (first || !live) ? Lc[i] : Lc[i] - Eo[i];
+                    mp.add(fabsf(M), i);
+                    sg |= (M < 0.0f ? 1u : 0u) << i;
+                }
+            }
+        }
+        if (!syn_only && live) {
+            const uint32_t neg = __popc(sg) & 1u;
+            const float m1 = ms_scale<CN>(mp.min1, param), m2 = ms_scale<CN>(mp.min2, param);
+#pragma unroll
+            for (int i = 0; i < kDeg; ++i) {
+                if (i < deg) {
+                    const float mag = i == mp.arg ? m2 : m1;
+                    st_e32(&Et[(beg + i) * kTile], ((neg ^ (sg >> i)) & 1u) ? -mag : mag);
+                }
+            }
+        }
+        return hp;
+    }
     float ph[kDeg];
     float S = 0.0f;
 #pragma unroll
@@ -130,11 +160,11 @@ __device__ __forceinline__ uint32_t phys_row(float *__restrict__ Et, int beg, in
 // (Batching the loads of 2 or 4 rows before any row's math measured 1.5-3 %
 // slower once phi was cheap: the extra registers cost occupancy,
 // profiles/r6_ab/r6e_c5.)
-template <int kDeg>
+template <int kDeg, int CN>
 __global__ __launch_bounds__(256) void phys_cn_tile_kernel(DevGraph g, DevState st, PhysTile pt, int it,
                                                            int syn_only, int per_tile, int items,
                                                            const int *__restrict__ row_ptr,
-                                                           const int *__restrict__ col_idx) {
+                                                           const int *__restrict__ col_idx, float param) {
     const int lane = threadIdx.x & 63;
     const int wave = uniform(threadIdx.x >> 6);
     for (int item = blockIdx.x; item < items; item += gridDim.x) {
@@ -166,18 +196,20 @@ __global__ __launch_bounds__(256) void phys_cn_tile_kernel(DevGraph g, DevState 
                     if (readE) Eo[i] = ld_e32(&Et[(beg + i) * kTile]);
                 }
             }
-            bad |= phys_row<kDeg>(Et, beg, deg, Lc, Eo, first, live, syn_only != 0);
+            bad |= phys_row<kDeg, CN>(Et, beg, deg, Lc, Eo, first, live, syn_only != 0, param);
         } else {
             const int end = beg + deg;
             uint32_t hp = 0u;
-            float S = 0.0f;
+            [[maybe_unused]] float S = 0.0f;
             uint32_t neg = 0u;
+            [[maybe_unused]] MinPair mp;
             for (int e = beg; e < end; ++e) {
                 const float Lc = live ? Lt[col_idx[e] * kTile] : 0.0f;
                 hp ^= Lc < 0.0f ? 1u : 0u;
                 if (!syn_only) {
                     const float M = (first || !live) ? Lc : Lc - Et[e * kTile];
-                    S += phi(fabsf(M));
+                    if constexpr (CN == kCnSpa) S += phi(fabsf(M));
+                    else mp.add(fabsf(M), e);
                     neg ^= (M < 0.0f) ? 1u : 0u;
                 }
             }
@@ -185,7 +217,9 @@ __global__ __launch_bounds__(256) void phys_cn_tile_kernel(DevGraph g, DevState 
                 for (int e = beg; e < end; ++e) {
                     const float Lc = Lt[col_idx[e] * kTile];
                     const float M = first ? Lc : Lc - ld_e32(&Et[e * kTile]);
-                    const float mag = phi(fmaxf(S - phi(fabsf(M)), 0.0f));
+                    float mag;
+                    if constexpr (CN == kCnSpa) mag = phi(fmaxf(S - phi(fabsf(M)), 0.0f));
+                    else mag = ms_scale<CN>(mp.other(e), param);
                     st_e32(&Et[e * kTile], ((neg ^ ((M < 0.0f) ? 1u : 0u)) != 0u) ? -mag : mag);
                 }
             }
@@ -475,18 +509,36 @@ hipError_t launch_phys_tile_init(const DevGraph &g, const DevState &st, const Ph
     return hipGetLastError();
 }
 
-hipError_t launch_phys_tile_cn(const DevGraph &g, const DevState &st, const PhysTile &pt, int it, bool syn_only,
-                               hipStream_t s) {
+namespace {
+
+template <int CN>
+void launch_cn_tile_rule(const DevGraph &g, const DevState &st, const PhysTile &pt, int it, bool syn_only,
+                         float param, hipStream_t s) {
     const int per_tile = (g.m + 4 * kRowsPerWave - 1) / (4 * kRowsPerWave);
     const int items = (int)xcd_items(st.ntiles, per_tile);
     const unsigned grid = stride_grid(items);
     const int so = syn_only ? 1 : 0;
     if (g.max_row_deg <= 8)
-        phys_cn_tile_kernel<8><<<grid, 256, 0, s>>>(g, st, pt, it, so, per_tile, items, g.row_ptr, g.col_idx);
+        phys_cn_tile_kernel<8, CN><<<grid, 256, 0, s>>>(g, st, pt, it, so, per_tile, items, g.row_ptr, g.col_idx,
+                                                        param);
     else if (g.max_row_deg <= 16)
-        phys_cn_tile_kernel<16><<<grid, 256, 0, s>>>(g, st, pt, it, so, per_tile, items, g.row_ptr, g.col_idx);
+        phys_cn_tile_kernel<16, CN><<<grid, 256, 0, s>>>(g, st, pt, it, so, per_tile, items, g.row_ptr, g.col_idx,
+                                                         param);
     else
-        phys_cn_tile_kernel<32><<<grid, 256, 0, s>>>(g, st, pt, it, so, per_tile, items, g.row_ptr, g.col_idx);
+        phys_cn_tile_kernel<32, CN><<<grid, 256, 0, s>>>(g, st, pt, it, so, per_tile, items, g.row_ptr, g.col_idx,
+                                                         param);
+}
+
+}  // namespace
+
+hipError_t launch_phys_tile_cn(const DevGraph &g, const DevState &st, const PhysTile &pt, int it, bool syn_only,
+                               hipStream_t s, const PhysRule &rule) {
+    switch (rule.cn) {
+    case kCnSpa: launch_cn_tile_rule<kCnSpa>(g, st, pt, it, syn_only, rule.param, s); break;
+    case kCnNms: launch_cn_tile_rule<kCnNms>(g, st, pt, it, syn_only, rule.param, s); break;
+    case kCnOms: launch_cn_tile_rule<kCnOms>(g, st, pt, it, syn_only, rule.param, s); break;
+    default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

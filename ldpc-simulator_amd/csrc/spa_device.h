@@ -195,13 +195,33 @@ hipError_t launch_export_frames(const DevGraph &g, const DevState &st, uint8_t *
 hipError_t launch_count(const DevGraph &g, const DevState &st, unsigned long long *counters,
                         hipStream_t s);
 
+// physical mode: check-node rule (LDPC_CN_*) and, for the layered schedule,
+// the graph's layer table on the device (ldpc_api.cpp builds it on first use)
+constexpr int kCnSpa = 0, kCnNms = 1, kCnOms = 2;
+struct PhysRule {
+    int cn = kCnSpa;
+    float param = 0.0f;             // alpha (kCnNms) or beta (kCnOms)
+    const int *layer_ptr = nullptr;  // [n_layers + 1]; null: flooding
+    const int *layer_rows = nullptr; // [m]
+    int n_layers = 0;
+    int max_layer = 0;              // rows of the largest layer
+};
+
 // physical mode (phys_kernels.hip)
 size_t phys_lds_bytes(const DevGraph &g);
 int phys_block_threads(const DevGraph &g);  // threads per workgroup launch_phys uses
 // layout 0: llr [count][n] fp64; 1: llr = ch tile layout; 2: lam [count][n] fp32 Lambda
 hipError_t launch_phys(const DevGraph &g, const double *llr, const float *lam, int layout, int count, int max_iter,
                        uint8_t *z, int *conv, int *status, int *iters, float *post, const uint32_t *ubits,
-                       unsigned long long *ctr, int grid, hipStream_t s);
+                       unsigned long long *ctr, int grid, hipStream_t s, const PhysRule &rule = PhysRule{});
+// layered min-sum (phys_layered.hip): E and L of a frame in LDS, one workgroup
+// barrier per layer; rule.cn is kCnNms or kCnOms and the layer table is set
+size_t phys_layered_lds_bytes(const DevGraph &g);
+int phys_layered_threads(const PhysRule &rule);
+hipError_t launch_phys_layered(const DevGraph &g, const double *llr, const float *lam, int layout, int count,
+                               int max_iter, uint8_t *z, int *conv, int *status, int *iters, float *post,
+                               const uint32_t *ubits, unsigned long long *ctr, int grid, hipStream_t s,
+                               const PhysRule &rule);
 
 // physical mode, HBM-resident tiles + IRA frame source (phys_tile.hip)
 // on-device frames of a chunk (frame_kernels.hip): info bits -> st.ubits,
@@ -217,7 +237,7 @@ hipError_t launch_frames(const DevGraph &g, const DevState &st, const PhysTile &
 hipError_t launch_phys_tile_init(const DevGraph &g, const DevState &st, const PhysTile &pt, bool convert,
                                  hipStream_t s);
 hipError_t launch_phys_tile_cn(const DevGraph &g, const DevState &st, const PhysTile &pt, int it, bool syn_only,
-                               hipStream_t s);
+                               hipStream_t s, const PhysRule &rule = PhysRule{});
 // active_count[it] += tiles that still have a running frame after VN(it)
 hipError_t launch_phys_tile_vn(const DevGraph &g, const DevState &st, const PhysTile &pt, int it, int *active_count,
                                int max_iter, hipStream_t s);  // active_count [2 max_iter]: tiles, then frames

@@ -7,12 +7,13 @@ is not a valid Python identifier; the reference itself runs as flat modules on
 sys.path, python_ldpc_app/main.py).
 """
 from ._lib import LdpcError, device_count, lib  # noqa: F401
-from .code import EncoderDecoderData, build_standard_form, csr_fingerprint, load_committed_code  # noqa: F401
+from .code import (EncoderDecoderData, build_layers, build_standard_form, csr_fingerprint,  # noqa: F401
+                   load_committed_code)
 from .enums import Result  # noqa: F401
 from .settings import Settings  # noqa: F401
 
 __all__ = ["EncoderDecoderData", "Settings", "Result", "SPA_Decoder", "Graph", "Decoder",
-           "build_standard_form", "csr_fingerprint", "load_committed_code", "device_count", "LdpcError"]
+           "build_standard_form", "build_layers", "csr_fingerprint", "load_committed_code", "device_count", "LdpcError"]
 
 
 def __getattr__(name):  # lazy: the decoder classes touch the GPU only when used

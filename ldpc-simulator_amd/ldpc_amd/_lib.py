@@ -31,6 +31,9 @@ LDPC_F_TEST_ZERO = 0x20  # test only: frame-source erasures (include/ldpc_hip.h)
 LDPC_MC_NCOUNT = 7
 LDPC_EINVAL = -22  # include/ldpc_hip.h error codes used on the Python side
 LDPC_ERANGE = -34
+# physical mode: check-node rules and schedules (include/ldpc_hip.h)
+LDPC_CN_SPA, LDPC_CN_NMS, LDPC_CN_OMS = 0, 1, 2
+LDPC_SCHED_FLOODING, LDPC_SCHED_LAYERED = 0, 1
 
 # every symbol include/ldpc_hip.h declares
 EXPORTED = (
@@ -42,6 +45,7 @@ EXPORTED = (
     "ldpc_decode_f64", "ldpc_generate_frames", "ldpc_mc_run", "ldpc_frame_order",
     "ldpc_profile_enable", "ldpc_profile_read", "ldpc_rare_rows_read",
     "ldpc_phys_lds_bytes", "ldpc_phys_decode", "ldpc_phys_mc_run",
+    "ldpc_phys_decode_ex", "ldpc_phys_mc_run_ex", "ldpc_phys_kernel_name_ex", "ldpc_layers_build",
     "ldpc_comm_unique_id", "ldpc_comm_init", "ldpc_comm_allreduce", "ldpc_comm_barrier", "ldpc_comm_destroy",
     "ldpc_device_synchronize",
 )
@@ -63,6 +67,7 @@ LDPC_EFORK = -100  # Python-side code: HIP was started in a parent process befor
 P = ctypes.POINTER
 c_i32, c_i64, c_u32, c_u64, c_dbl, c_vp = (ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32,
                                            ctypes.c_uint64, ctypes.c_double, ctypes.c_void_p)
+c_flt = ctypes.c_float
 
 
 def _declare(lib):
@@ -97,6 +102,12 @@ def _declare(lib):
         "ldpc_phys_decode": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
         "ldpc_phys_mc_run": (ctypes.c_int, [c_vp, c_vp, c_u64, c_i32, P(c_dbl), c_i64, c_i64, c_i32, c_u32,
                                             P(c_i64), c_vp]),
+        "ldpc_phys_decode_ex": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32, c_u32, c_i32, c_i32, c_flt, c_vp, c_vp,
+                                               c_vp, c_vp, c_vp, c_vp]),
+        "ldpc_phys_mc_run_ex": (ctypes.c_int, [c_vp, c_vp, c_u64, c_i32, P(c_dbl), c_i64, c_i64, c_i32, c_u32,
+                                               c_i32, c_i32, c_flt, P(c_i64), c_vp]),
+        "ldpc_phys_kernel_name_ex": (ctypes.c_char_p, [c_vp, c_u32, c_i32, c_i32]),
+        "ldpc_layers_build": (ctypes.c_int, [c_i32, c_i32, P(c_i32), P(c_i32), P(c_i32), P(c_i32)]),
         "ldpc_profile_read": (ctypes.c_int, [c_vp, P(c_dbl), P(c_i64)]),
         "ldpc_rare_rows_read": (ctypes.c_int, [c_vp, P(c_i64)]),
         "ldpc_comm_unique_id": (ctypes.c_int, [c_vp]),

@@ -52,6 +52,28 @@ def build_standard_form(H):
     return Hs, perm.tolist()
 
 
+def build_layers(H):
+    """The layered schedule's layers of H (ldpc_layers_build: first-fit over
+    the rows in ascending order; rows of a layer share no column).
+
+    Returns (layer_ptr [layers + 1], layer_rows [m]) as int32 arrays: layer l
+    holds rows layer_rows[layer_ptr[l]:layer_ptr[l + 1]], ascending.  Host only."""
+    H = sparse.csr_matrix(H)
+    if not H.has_sorted_indices:
+        H = H.sorted_indices()
+    m, n = H.shape
+    indptr, indices = as_i32(H.indptr), as_i32(H.indices)
+    of_row = np.empty(max(m, 1), np.int32)
+    nl = ctypes.c_int32()
+    check("ldpc_layers_build", _lib.lib().ldpc_layers_build(m, n, _lib.i32p(indptr), _lib.i32p(indices),
+                                                            _lib.i32p(of_row), ctypes.byref(nl)))
+    of_row = of_row[:m]
+    layer_ptr = np.zeros(nl.value + 1, np.int32)
+    np.cumsum(np.bincount(of_row, minlength=nl.value), out=layer_ptr[1:])
+    layer_rows = np.argsort(of_row, kind="stable").astype(np.int32)
+    return layer_ptr, layer_rows
+
+
 def csr_fingerprint(H):
     """sha256(int32-LE indptr || int32-LE indices) -- SURVEY.md §8c convention."""
     H = sparse.csr_matrix(H)

@@ -103,10 +103,46 @@ class Graph:
         self._h = None
 
 
-def phys_decode(graph, llr, max_iter, post=False, hbm=False):
+CN_RULES = {"spa": _lib.LDPC_CN_SPA, "nms": _lib.LDPC_CN_NMS, "oms": _lib.LDPC_CN_OMS}
+SCHEDULES = {"flooding": _lib.LDPC_SCHED_FLOODING, "layered": _lib.LDPC_SCHED_LAYERED}
+
+
+def phys_rule_args(cn="spa", schedule="flooding", alpha=0.75, beta=0.5):
+    """(cn_rule, schedule, param) of the C ABI for the physical-mode options:
+    cn "spa" (sum-product), "nms" (normalized min-sum, alpha in (0, 1]) or
+    "oms" (offset min-sum, beta >= 0); schedule "flooding" or "layered".
+    Raises ValueError for anything else -- before any device call."""
+    if cn not in CN_RULES:
+        raise ValueError(f"cn must be one of {sorted(CN_RULES)}, got {cn!r}")
+    if schedule not in SCHEDULES:
+        raise ValueError(f"schedule must be one of {sorted(SCHEDULES)}, got {schedule!r}")
+    alpha, beta = float(alpha), float(beta)
+    if cn == "nms" and not (0.0 < alpha <= 1.0):
+        raise ValueError(f"alpha must be in (0, 1], got {alpha}")
+    if cn == "oms" and not beta >= 0.0:
+        raise ValueError(f"beta must be >= 0, got {beta}")
+    if cn == "spa" and schedule == "layered":
+        raise ValueError("the layered schedule needs a min-sum rule (cn='nms' or 'oms'): "
+                         "sum-product layered is not implemented")
+    return CN_RULES[cn], SCHEDULES[schedule], {"spa": 0.0, "nms": alpha, "oms": beta}[cn]
+
+
+def phys_kernel_name(graph, hbm=False, cn="spa", schedule="flooding"):
+    """Measurement label: the kernel phys_decode runs for these options."""
+    rule, sched, _ = phys_rule_args(cn, schedule)
+    return _lib.gpu().ldpc_phys_kernel_name_ex(graph.handle, LDPC_F_PHYS_HBM if hbm else 0, rule, sched).decode()
+
+
+def phys_decode(graph, llr, max_iter, post=False, hbm=False, cn="spa", schedule="flooding", alpha=0.75, beta=0.5,
+                ex=False):
     """Physical-mode decode of [B, n] LLRs on a sparse graph (H[:, perm]).
 
-    State in LDS when a frame fits, else in HBM (hbm=True forces HBM)."""
+    State in LDS when a frame fits, else in HBM (hbm=True forces HBM).
+    cn / schedule / alpha / beta: phys_rule_args; the defaults are the
+    sum-product flooding decoder (ldpc_phys_decode), anything else goes through
+    ldpc_phys_decode_ex (ex=True: the defaults too -- the library takes the
+    same path for them either way; tests).  Layered runs on the LDS path only."""
+    rule, sched, param = phys_rule_args(cn, schedule, alpha, beta)
     llr = np.ascontiguousarray(np.atleast_2d(np.asarray(llr, dtype=np.float64)))
     B, n = llr.shape
     if n != graph.n:
@@ -116,10 +152,15 @@ def phys_decode(graph, llr, max_iter, post=False, hbm=False):
     status = np.empty(B, np.int32)
     iters = np.empty(B, np.int32)
     Lp = np.empty((B, n), np.float32) if post else None
-    check("ldpc_phys_decode", _lib.gpu().ldpc_phys_decode(
-        graph.handle, B, _lib.ptr(llr), int(max_iter), LDPC_F_PHYS_HBM if hbm else 0, _lib.ptr(z), _lib.ptr(conv),
-        _lib.ptr(status),
-        _lib.ptr(iters), _lib.ptr(Lp), None))
+    flags = LDPC_F_PHYS_HBM if hbm else 0
+    if (cn, schedule) == ("spa", "flooding") and not ex:
+        check("ldpc_phys_decode", _lib.gpu().ldpc_phys_decode(
+            graph.handle, B, _lib.ptr(llr), int(max_iter), flags, _lib.ptr(z), _lib.ptr(conv), _lib.ptr(status),
+            _lib.ptr(iters), _lib.ptr(Lp), None))
+    else:
+        check("ldpc_phys_decode_ex", _lib.gpu().ldpc_phys_decode_ex(
+            graph.handle, B, _lib.ptr(llr), int(max_iter), flags, rule, sched, param, _lib.ptr(z), _lib.ptr(conv),
+            _lib.ptr(status), _lib.ptr(iters), _lib.ptr(Lp), None))
     return DecodeResult(z=z, conv=conv, status=status, iters=iters, post=Lp)
 
 
@@ -246,17 +287,24 @@ class Decoder:
             self._h, int(seed), int(snr_point), float(sigma), int(frame0), int(count), _lib.ptr(out), None))
         return out
 
-    def phys_mc_run(self, phys_graph, seed, sigmas, frames_per_point, frame0, max_iter, hbm=False):
+    def phys_mc_run(self, phys_graph, seed, sigmas, frames_per_point, frame0, max_iter, hbm=False, cn="spa",
+                    schedule="flooding", alpha=0.75, beta=0.5):
         """Physical mode (§8 f4): same on-device frames, decoded on the sparse graph.
 
         This decoder's graph is the code's H_std (frame source) or, for an IRA
-        code, phys_graph itself.  hbm=True forces the HBM-resident tile path."""
+        code, phys_graph itself.  hbm=True forces the HBM-resident tile path.
+        cn / schedule / alpha / beta as phys_decode (the defaults are
+        ldpc_phys_mc_run, anything else ldpc_phys_mc_run_ex)."""
+        rule, sched, param = phys_rule_args(cn, schedule, alpha, beta)
         sig = np.ascontiguousarray(np.asarray(sigmas, dtype=np.float64))
         out = np.zeros((len(sig), LDPC_MC_NCOUNT), np.int64)
-        check("ldpc_phys_mc_run", _lib.gpu().ldpc_phys_mc_run(
-            self._h, phys_graph.handle, int(seed), len(sig), sig.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-            int(frames_per_point), int(frame0), int(max_iter), LDPC_F_PHYS_HBM if hbm else 0,
-            out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), None))
+        head = (self._h, phys_graph.handle, int(seed), len(sig), sig.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                int(frames_per_point), int(frame0), int(max_iter), LDPC_F_PHYS_HBM if hbm else 0)
+        tail = (out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), None)
+        if (cn, schedule) == ("spa", "flooding"):
+            check("ldpc_phys_mc_run", _lib.gpu().ldpc_phys_mc_run(*head, *tail))
+        else:
+            check("ldpc_phys_mc_run_ex", _lib.gpu().ldpc_phys_mc_run_ex(*head, rule, sched, param, *tail))
         return out
 
     KINDS = ("cn", "vn", "generate", "count", "phys", "phys_cn", "phys_vn", "tile", "cn_edge", "vn_edge",

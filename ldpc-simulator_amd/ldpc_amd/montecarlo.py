@@ -91,11 +91,30 @@ def run_sweep(decoder, snrs, blocks, max_iter, seed=20260213, nllr=False, speed=
     return local
 
 
+DECODER_TYPES = {"spa": "sumproduct", "nms": "minsum-normalized", "oms": "minsum-offset"}
+
+
+def decoder_type(cn_rule="spa", schedule="flooding"):
+    """The result schema's decoder_type for a check rule and schedule."""
+    return DECODER_TYPES[cn_rule] + ("-layered" if schedule == "layered" else "")
+
+
 def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65536, device=0,
-             rank=0, world=1, allreduce=None, matrix_path=""):
-    """Full sweep on this process's GPU -> SimulationResult (reference schema)."""
+             rank=0, world=1, allreduce=None, matrix_path="", mode="parity", cn_rule="spa", schedule="flooding",
+             alpha=0.75, beta=0.5):
+    """Full sweep on this process's GPU -> SimulationResult (reference schema).
+
+    mode "parity" is the reference's decoder on H_std; "physical" decodes the
+    same on-device frames on the sparse graph (Decoder.phys_mc_run) with the
+    check rule cn_rule ("spa", "nms", "oms"; alpha / beta) and the schedule
+    ("flooding", "layered") -- those options need mode="physical"."""
     from .code import EncoderDecoderData, load_committed_code
-    from .device import Decoder, Graph
+    from .device import Decoder, Graph, phys_rule_args
+    if mode not in ("parity", "physical"):
+        raise ValueError(f"mode must be 'parity' or 'physical', got {mode!r}")
+    phys_rule_args(cn_rule, schedule, alpha, beta)  # ValueError before any device call
+    if mode == "parity" and (cn_rule, schedule) != ("spa", "flooding"):
+        raise ValueError("cn_rule / schedule need mode='physical' (parity mode is the reference's sum-product)")
     t0 = time.time()
     if isinstance(matrix, EncoderDecoderData):
         edd = matrix
@@ -105,19 +124,26 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
         edd = load_committed_code(matrix)
     g = Graph(edd._h_std, device=device)
     dec = Decoder(g, Decoder.fit_slots(g, min(max(1, shard(int(blocks), rank, world)[1]), chunk)))
+    counter_fn = None
+    if mode == "physical":
+        gp = Graph(edd.physical_matrix(), device=device)
+
+        def counter_fn(sigmas, cnt, frame0):
+            return dec.phys_mc_run(gp, seed, sigmas, cnt, frame0, max_iter, cn=cn_rule, schedule=schedule,
+                                   alpha=alpha, beta=beta)
     ctr = run_sweep(dec, snrs, blocks, max_iter, seed=seed, nllr=nllr, rank=rank, world=world,
-                    allreduce=allreduce)
+                    allreduce=allreduce, counter_fn=counter_fn)
     pts = point_results(ctr, edd._k, snrs, matrix_path=matrix_path or str(matrix), max_iter=max_iter)
     cfg = SimulationConfig(
         matrix_path=matrix_path or str(matrix), n=edd._n, m=edd._m, k=edd._k, rate=edd._rate,
         blocks=int(blocks), max_iterations=int(max_iter), encoding_method="standard",
-        interleaver_type="none", decoder_type="sumproduct", channel_mode=1, modulation=1,
+        interleaver_type="none", decoder_type=decoder_type(cn_rule, schedule), channel_mode=1, modulation=1,
         speed=1.0, snr_range=(snrs[0], snrs[-1], (snrs[1] - snrs[0]) if len(snrs) > 1 else 0.0),
         threads=world, timestamp=datetime.now().isoformat())
     return SimulationResult(config=cfg, snr_points=pts, wall_clock_seconds=time.time() - t0), ctr
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description="GPU BER/FER sweep (main.py semantics, AWGN mode 1, BPSK)")
     ap.add_argument("--matrix", required=True, help="ALIST path or a committed code name")
     ap.add_argument("-b", "--blocks", type=int, default=1000)
@@ -129,7 +155,37 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=20260213)
     ap.add_argument("--output-json")
     ap.add_argument("--output-csv")
+    ap.add_argument("--mode", choices=("parity", "physical"), default="parity",
+                    help="parity: the reference's decoder on H_std; physical: the sparse graph, fp32")
+    ap.add_argument("--cn-rule", choices=("spa", "nms", "oms"), default="spa",
+                    help="physical mode: sum-product, normalized or offset min-sum")
+    ap.add_argument("--schedule", choices=("flooding", "layered"), default="flooding",
+                    help="physical mode: layered needs a min-sum rule")
+    ap.add_argument("--alpha", type=float, default=None, help="normalized min-sum factor in (0, 1] (default 0.75)")
+    ap.add_argument("--beta", type=float, default=None, help="offset min-sum offset >= 0 (default 0.5)")
+    return ap
+
+
+def parse_args(argv=None):
+    """Parse the command line; the physical-mode options without --mode physical,
+    and combinations the decoder rejects, are argparse errors."""
+    from .device import phys_rule_args
+    ap = build_parser()
     a = ap.parse_args(argv)
+    if a.mode != "physical" and (a.cn_rule != "spa" or a.schedule != "flooding" or a.alpha is not None
+                                 or a.beta is not None):
+        ap.error("--cn-rule, --schedule, --alpha and --beta need --mode physical")
+    a.alpha = 0.75 if a.alpha is None else a.alpha
+    a.beta = 0.5 if a.beta is None else a.beta
+    try:
+        phys_rule_args(a.cn_rule, a.schedule, a.alpha, a.beta)
+    except ValueError as e:
+        ap.error(str(e))
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -140,7 +196,8 @@ def main(argv=None):
         allreduce = comm.allreduce
     snrs = snr_grid(a.initial_snr, a.end_snr, a.step_snr)
     res, _ = simulate(a.matrix, snrs, a.blocks, a.iterations, seed=a.seed, nllr=a.normalized_llr,
-                      device=local, rank=rank, world=world, allreduce=allreduce)
+                      device=local, rank=rank, world=world, allreduce=allreduce, mode=a.mode, cn_rule=a.cn_rule,
+                      schedule=a.schedule, alpha=a.alpha, beta=a.beta)
     if rank == 0:
         for sp in res.snr_points:
             print(f"SNR {sp.snr_db:.2f} dB  FER {sp.fer:.6f}  BER {sp.ber:.6e}  "

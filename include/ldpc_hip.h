@@ -31,7 +31,8 @@
 extern "C" {
 #endif
 
-#define LDPC_ABI_VERSION 5  /* 5: LDPC_F_TEST_ZERO + ldpc_rare_rows_read (4: profile kinds LDPC_K_NKINDS 11) */
+#define LDPC_ABI_VERSION 5  /* 5: LDPC_F_TEST_ZERO + ldpc_rare_rows_read (4: profile kinds LDPC_K_NKINDS 11);
+                             * ldpc_fixed_point_read was added under 5: an addition only, nothing else changed */
 
 /* error codes */
 #define LDPC_OK 0
@@ -296,6 +297,14 @@ int ldpc_profile_read(ldpc_decoder *d, double *ms_out, int64_t *launches_out);
  * out[1] = rare rows the tile-resident decoders took in-kernel (one per
  * workgroup, row and pass).  A test hook: which code path saw the branch. */
 int ldpc_rare_rows_read(ldpc_decoder *d, int64_t *out);
+/* Fixed-point exit of the static 16-frame sub-tile decoder (tile_sub_kernel:
+ * wimax_2304_0.5): a frame whose pass reproduced its messages and posteriors
+ * bit for bit stops there with the outputs it would have after max_iter passes
+ * (status 1, conv -1, iters = max_iter).  Since the last call, then reset
+ * (synchronises the device): out[0] = frames stopped this way, out[1] =
+ * frame-passes they did not execute.  LDPC_FIXED_POINT=0 (environment, read
+ * per launch) switches the exit off; results are identical either way. */
+int ldpc_fixed_point_read(ldpc_decoder *d, int64_t *out);
 
 /* ------------------------------------------------ multi-GPU (RCCL, xGMI)
  * One process per GPU; frames are sharded by global index, so the only

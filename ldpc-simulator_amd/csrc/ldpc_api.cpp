@@ -60,11 +60,15 @@ struct ldpc_graph {
     mutable int n_layers = 0, max_layer = 0;
 };
 
+// ints ahead of the rare-row list in ldpc_decoder::rare: 4 rare-row counts, 2 x 64-bit fixed-point totals
+constexpr int kRareHead = 8;
+
 struct ldpc_decoder {
     const ldpc_graph *g = nullptr;
     int cap_tiles = 0;
     double *E = nullptr, *T = nullptr, *L = nullptr, *ch = nullptr;
-    int *rare = nullptr;  // rare_count[2] + running totals[2] (ldpc_rare_rows_read) + rare_list[cap_tiles*m*4]
+    int *rare = nullptr;  // rare_count[2] + running totals[2] (ldpc_rare_rows_read) + fixed-point totals (2 x 64 bit,
+                          // ldpc_fixed_point_read) + rare_list[cap_tiles*m*4]
     int nslots = 0;
     int *ints = nullptr;  // done, conv, status, iters, nllr_cnt, fresh, refill (cap frames each) + tile_active
     uint32_t *ubits = nullptr;
@@ -240,7 +244,8 @@ void state_bind(ldpc_decoder *d, int ntiles, int count) {
     s.T = d->T;
     s.rare_count = d->rare;
     s.active_count = nullptr;
-    s.rare_list = d->rare + 4;
+    s.fp_count = reinterpret_cast<unsigned long long *>(d->rare + 4);  // 16 bytes into a hipMalloc block
+    s.rare_list = d->rare + kRareHead;
     s.nslots = d->nslots;
     s.L = d->L;
     s.ch = d->ch;
@@ -432,7 +437,7 @@ size_t workspace_bytes(const DevGraph &g, int cap_tiles) {
     b += cap * (size_t)g.nnz * 8;                                   // E
     const size_t slots = ldpc::use_tile(g) ? std::max(scratch_slots(), cap_tiles * tile_scratch_rows(g)) : scratch_slots();
     b += slots * g.max_row_deg * kTile * 8;  // T pool
-    b += 4 * (4 + (size_t)cap_tiles * g.m * 4);                           // rare counts + list
+    b += 4 * (kRareHead + (size_t)cap_tiles * g.m * 4);                   // rare + fixed-point counts, rare list
     b += 2 * cap * (size_t)g.n * 8;    // L, ch
     b += (7 * cap + cap_tiles) * 4;    // per-frame ints + tile flags
     b += cap * kw * 4;                 // ubits
@@ -727,8 +732,8 @@ int ldpc_decoder_create(const ldpc_graph *g, int32_t max_frames, ldpc_decoder **
         return ldpc_fail(LDPC_ERANGE, "ldpc_decoder_create: %d frames x %d rows exceed the rare-row list", max_frames,
                          G.m);
     }
-    if (!rc) rc = dev_alloc(&d->rare, 4 + (size_t)d->cap_tiles * G.m * 4);
-    if (!rc && hipMemset(d->rare, 0, sizeof(int) * 4) != hipSuccess)
+    if (!rc) rc = dev_alloc(&d->rare, kRareHead + (size_t)d->cap_tiles * G.m * 4);
+    if (!rc && hipMemset(d->rare, 0, sizeof(int) * kRareHead) != hipSuccess)
         rc = ldpc_fail(LDPC_EDEVICE, "ldpc_decoder_create: memset failed");
     if (!rc) rc = dev_alloc(&d->L, cap * (size_t)G.n);
     if (!rc) rc = dev_alloc(&d->ch, cap * (size_t)G.n);
@@ -1246,6 +1251,18 @@ int ldpc_rare_rows_read(ldpc_decoder *d, int64_t *out) {
     HIP_TRY(hipMemset(d->rare + 2, 0, sizeof h));
     out[0] = h[0];
     out[1] = h[1];
+    return LDPC_OK;
+}
+
+int ldpc_fixed_point_read(ldpc_decoder *d, int64_t *out) {
+    if (!d || !out) return ldpc_fail(LDPC_EINVAL, "ldpc_fixed_point_read: bad arguments");
+    DeviceGuard dg(d->g->device);
+    unsigned long long h[2] = {0, 0};
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(h, d->rare + 4, sizeof h, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemset(d->rare + 4, 0, sizeof h));
+    out[0] = (int64_t)h[0];
+    out[1] = (int64_t)h[1];
     return LDPC_OK;
 }
 

@@ -68,6 +68,8 @@ struct DevState {
     int *rare_list;          // [ntiles*m] tile*m+row of rows left to cn_rare_kernel
     int *rare_count;         // [2] per iteration parity, then two running totals (ldpc_rare_rows_read):
                              // [2] rows cn_rare_kernel took, [3] rare rows the tile decoders took in-kernel
+    unsigned long long *fp_count;  // [2] running totals of tile_sub_kernel's fixed-point exit (ldpc_fixed_point_read):
+                             // frames stopped at a bitwise fixed point, frame-passes they did not execute
     int *active_count;       // [max_iter] or null: vn_kernel adds the tiles still running after it
     int nslots;
     uint32_t *ubits;         // MC only (may be null)

@@ -206,6 +206,8 @@ struct SubCtx {
     int ep0;
     bool first, live;
     bool fresh;  // streaming: this lane's frame is on its first pass (M = L - 0, L = ch)
+    bool verify;  // static decoder: this pass verifies a fixed point (sub_p3_body compares E_new with E_old)
+    int *mdiff;   // LDS [F]: verifying pass, a message of frame f differed
     int ntiny;
 #ifdef LDPC_SUB_TIMERS
     mutable uint64_t tm[SUB_NT];
@@ -540,6 +542,26 @@ __device__ __forceinline__ void sub_p3_body(SubCtx<Q> &c, int r, double (&t)[Sub
             }
         }
     }
+    if (c.verify) {
+        // The verifying pass of the static decoder's fixed-point exit
+        // (tile_sub_kernel; uniform, false on every other pass): the E_old that
+        // each own E_new store replaces is loaded again through the buffer
+        // resource (masked slots at kSubOOB request nothing) and compared with
+        // E_new bit for bit; a difference sets the frame's flag.  The loads
+        // are compared, so they have returned, before the stores below issue.
+        // Here and not ahead of the chain wait: E_old held from there costs 20
+        // registers of every pass's row loop, this block none outside itself.
+        const uint32_t eoff = sub_eoff(c, rc);
+        const int njv = c.live ? nj : 0;
+        double eold[K];
+#pragma unroll
+        for (int i = 0; i < K; ++i)
+            eold[i] = ld_sub_msg(c.rE, i < njv ? eoff + (uint32_t)i * (kTile * sizeof(double)) : kSubOOB);
+        bool d = false;
+#pragma unroll
+        for (int i = 0; i < K; ++i) d |= i < njv && dbits(eold[i]) != dbits(t[i]);
+        if (d) atomicOr((uint32_t *)c.mdiff + (threadIdx.x & (F - 1)), 1u);
+    }
     {
         const uint32_t eoff = sub_eoff(c, rc);
 #pragma unroll
@@ -623,12 +645,35 @@ __device__ __forceinline__ void sub_body(SubCtx<Q> &c, int r, int m, double (&tc
     SUB_ADD(c, 6, p0, p1);
 }
 
+// Fixed-point exit (fp != 0; LDPC_FIXED_POINT=0 switches it off).  A pass is a
+// deterministic function of (E, L) and ch, its summation order fixed by the
+// p3dep waits, so a frame whose pass reproduced E and L bit for bit repeats
+// that state on every later pass: it stops there with the outputs of pass
+// max_iter (failed frames at low SNR: the headline's frames stop after 3-5 of
+// 50 passes).  Nothing approximate:
+//   trigger  the column sweep compares each A-column posterior with the
+//            previous one (ch on iteration 0) bit for bit: pdiffl[f];
+//   verify   a pass at iteration >= 1, when some running frame's posteriors
+//            repeated in the pass before, compares every own E_new with the
+//            E_old it replaces (c.verify, sub_p3_body): mdiffl[f].  The
+//            identity columns need no check: for iteration >= 1
+//            L = ch + (0 + E) of the row's last edge repeats if E does;
+//   exit     after a verifying pass, a running frame with no message and no
+//            posterior difference in that pass (syndrome non-zero: a zero one
+//            took the OK exit) stops as DATA_TRANSFER_NOT_OK after max_iter
+//            iterations; its normalized-LLR history continues with the 0 that
+//            every later pass would count (ap == Lj);
+//   back-off a verifying pass that confirmed no frame is followed by a gap of
+//            1, 2, 4, ... passes before the next: at most 6 unconfirmed
+//            verifying passes (iterations 1, 3, 6, 11, 20, 37) at T = 50.
+// st.fp_count: frames stopped this way, frame-passes not executed.
 template <int Q>
 __global__ __launch_bounds__(64 * kSW, 1) void tile_sub_kernel(DevGraph g, DevState st, int max_iter, int nllr,
                                                                const int *__restrict__ col_idx,
-                                                               const int *__restrict__ row_ptr, AtanhCoef ac) {
+                                                               const int *__restrict__ row_ptr, AtanhCoef ac, int fp) {
     constexpr int F = SubCfg<Q>::F, K = SubCfg<Q>::K;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    __shared__ int pdiffl[F], mdiffl[F];  // per frame: a posterior / a message differed in this pass
     const SubLayout ly = sub_layout(g.k, g.m, F);
     double *S = (double *)(lds + ly.S);
     MathLds &mlds = *(MathLds *)(lds + ly.math);
@@ -652,7 +697,11 @@ __global__ __launch_bounds__(64 * kSW, 1) void tile_sub_kernel(DevGraph g, DevSt
     const int wave = uniform(sub_wave(threadIdx.x >> 6));
     const int j = lane / F, f = lane % F;
     const int fr = tile * kTile + sub * F + f;  // this lane's frame
-    if (wave == 0 && j == 0) livel[f] = st.done[fr] == 0 ? 1 : 0;
+    if (wave == 0 && j == 0) {
+        livel[f] = st.done[fr] == 0 ? 1 : 0;
+        pdiffl[f] = 0;
+        mdiffl[f] = 0;
+    }
     __syncthreads();
     if (!st.tile_active[tile]) return;
     {  // a sub-tile with no live frame (a ragged batch's last tile) has nothing to do
@@ -697,6 +746,7 @@ __global__ __launch_bounds__(64 * kSW, 1) void tile_sub_kernel(DevGraph g, DevSt
     c.f = f;
     c.ntiny = 0;
     c.fresh = false;
+    c.mdiff = mdiffl;
 #ifdef LDPC_SUB_TIMERS
     for (int i = 0; i < SUB_NT; ++i) c.tm[i] = 0;
 #endif
@@ -704,10 +754,17 @@ __global__ __launch_bounds__(64 * kSW, 1) void tile_sub_kernel(DevGraph g, DevSt
     const int nthr = kSW * Q;       // (wavefront, lane group) pairs
     const int me = wave * Q + j;    // this lane's pair
 
+    // fixed-point exit, uniform over the workgroup: ctl = the word wavefront 0
+    // left after the last pass (1: a frame still runs, 2: a running frame's
+    // posteriors repeated, 4: a frame stopped at a fixed point); the next
+    // verifying pass is allowed at iteration vnext, after a gap of vgap passes
+    int ctl = 1, vnext = 1, vgap = 1;
     for (int it = 0; it < max_iter; ++it) {
         c.first = it == 0;
         c.live = livel[f] != 0;
         c.ep0 = sub_epoch0(it, m);
+        const bool verify = fp != 0 && it >= vnext && (ctl & 2) != 0;
+        c.verify = verify;
         double tA[K], tB[K];
         bool yA = false, yB = false;
         if (m > 0) {
@@ -725,20 +782,23 @@ __global__ __launch_bounds__(64 * kSW, 1) void tile_sub_kernel(DevGraph g, DevSt
         // normalized-LLR count against the previous posterior (:210-228),
         // z^1 bits
         int my_cnt = 0;
+        bool pd = false;  // the fixed-point trigger: a posterior of this pass differs from the previous one
         for (int col = me; col < g.k; col += nthr) {
             double *sp = c.S + (size_t)col * F;
             const double Sj = *sp;
             *sp = 0.0;
             const double chj = *sub_c(c, col);
             const double Lj = chj + Sj;
-            if (nllr) {
+            if (nllr || fp) {
                 const double ap = c.first ? chj : ld_l2(sub_l(c, col));
-                my_cnt += (fabs(Lj) <= 7.0 && ap * Lj < 0.0) ? 1 : 0;
+                if (nllr) my_cnt += (fabs(Lj) <= 7.0 && ap * Lj < 0.0) ? 1 : 0;
+                pd |= dbits(ap) != dbits(Lj);
             }
             if (c.live) *sub_l(c, col) = Lj;
             if (!(Lj < 0.0)) atomicOr(zb + (col >> 5) * F + f, 1u << (col & 31));
         }
         if (nllr && my_cnt) atomicAdd(cntl + f, my_cnt);
+        if (fp && pd && c.live) atomicOr((uint32_t *)pdiffl + f, 1u);
         __syncthreads();
 
         // syndrome (:191-204): parity of row r = popcount(A_r & (z^1)_A) +
@@ -754,7 +814,7 @@ __global__ __launch_bounds__(64 * kSW, 1) void tile_sub_kernel(DevGraph g, DevSt
         __syncthreads();
 
         if (wave == 0) {  // per-frame exits, as vn_kernel (static schedule)
-            bool still = false;
+            bool still = false, fixed = false;
             if (j == 0 && c.live) {
                 if (nllr) {
                     const int cn = cntl[f];
@@ -772,21 +832,46 @@ __global__ __launch_bounds__(64 * kSW, 1) void tile_sub_kernel(DevGraph g, DevSt
                     st.conv[fr] = -1;
                     st.status[fr] = 1;
                     st.iters[fr] = it + 1;
+                } else if (verify && mdiffl[f] == 0 && pdiffl[f] == 0) {
+                    // a fixed point: every pass up to max_iter - 1 would leave E, L and z as they
+                    // are, count 0 sign changes and end as DATA_TRANSFER_NOT_OK
+                    st.done[fr] = 1;
+                    st.conv[fr] = -1;
+                    st.status[fr] = 1;
+                    st.iters[fr] = max_iter;
+                    if (nllr && st.nllr_hist)
+                        for (int i = it + 1; i < max_iter; ++i) st.nllr_hist[(size_t)fr * st.hist_stride + i] = 0.0;
+                    fixed = true;
                 } else {
                     still = true;
                 }
             }
             const unsigned long long any = __ballot(still);
+            const unsigned long long trig = __ballot(still && fp && pdiffl[f] == 0);
+            const int nfix = __popcll(__ballot(fixed));
             if (j == 0) {
                 livel[f] = still ? 1 : 0;
                 bad[f] = 0;
                 cntl[f] = 0;
+                pdiffl[f] = 0;
+                mdiffl[f] = 0;
             }
-            if (lane == 0) flags[2 * kSR + 1] = any != 0ull ? 1 : 0;
+            if (lane == 0) {
+                flags[2 * kSR + 1] = (any != 0ull ? 1 : 0) | (trig != 0ull ? 2 : 0) | (nfix ? 4 : 0);
+                if (nfix) {
+                    atomicAdd(&st.fp_count[0], (unsigned long long)nfix);
+                    atomicAdd(&st.fp_count[1], (unsigned long long)nfix * (unsigned long long)(max_iter - 1 - it));
+                }
+            }
         }
         for (int i = threadIdx.x; i < (kw + mw) * F; i += blockDim.x) zb[i] = 0u;
         __syncthreads();
-        if (!flags[2 * kSR + 1]) break;
+        ctl = uniform(flags[2 * kSR + 1]);
+        if (!(ctl & 1)) break;
+        if (verify && !(ctl & 4)) {  // nothing confirmed: back off
+            vnext = it + 1 + vgap;
+            vgap *= 2;
+        }
     }
     count_rare_rows(st, c.tseq, kSW);
 #ifdef LDPC_SUB_TIMERS
@@ -882,6 +967,8 @@ __global__ __launch_bounds__(64 * kSW, 1) void tile_sub_stream_kernel(
     c.f = f;
     c.ntiny = 0;
     c.first = false;
+    c.verify = false;  // the fixed-point exit is the static decoder's
+    c.mdiff = nullptr;
     const int m = g.m;
     const int nthr = kSW * Q;
     const int me = wave * Q + j;
@@ -1032,7 +1119,8 @@ size_t sub_lds_bytes_q(const DevGraph &g) {
     if (!g.std_form || !g.a_packed || g.k <= 0 || g.max_row_deg > kSW * Q * K || Q * K > 64 || g.n > 65535)
         return 0;
     const size_t b = sub_layout(g.k, g.m, F).total;
-    return b <= kSubLdsMax ? b : 0;
+    // + the static kernel's own 2 x F ints (tile_sub_kernel: pdiffl, mdiffl)
+    return b + 2 * F * sizeof(int) <= kSubLdsMax ? b : 0;
 }
 
 }  // namespace
@@ -1059,8 +1147,11 @@ hipError_t launch_tile_sub_stream(const DevGraph &g, const DevState &st, int max
 hipError_t launch_tile_sub(const DevGraph &g, const DevState &st, int max_iter, bool nllr, hipStream_t s) {
     const size_t lds = sub_lds_bytes(g);
     if (!lds || 2 * st.ntiles > st.nslots) return hipErrorInvalidValue;  // two rare-row buffers per workgroup
+    // LDPC_FIXED_POINT=0 (read per launch): no fixed-point exit, every frame makes its passes (A/B, diagnosis)
+    const char *e = getenv("LDPC_FIXED_POINT");
+    const int fp = (!e || atoi(e) != 0) ? 1 : 0;
     tile_sub_kernel<4><<<st.ntiles * 4, 64 * kSW, lds, s>>>(g, st, max_iter, nllr ? 1 : 0, g.col_idx, g.row_ptr,
-                                                            kAtanhCoef);
+                                                            kAtanhCoef, fp);
     return hipGetLastError();
 }
 

@@ -43,7 +43,7 @@ EXPORTED = (
     "ldpc_phys_kernel_name", "ldpc_tile_lds_bytes", "ldpc_tile_kernel_name",
     "ldpc_decoder_bytes", "ldpc_decoder_create", "ldpc_decoder_destroy", "ldpc_decoder_capacity",
     "ldpc_decode_f64", "ldpc_generate_frames", "ldpc_mc_run", "ldpc_frame_order",
-    "ldpc_profile_enable", "ldpc_profile_read", "ldpc_rare_rows_read",
+    "ldpc_profile_enable", "ldpc_profile_read", "ldpc_rare_rows_read", "ldpc_fixed_point_read",
     "ldpc_phys_lds_bytes", "ldpc_phys_decode", "ldpc_phys_mc_run",
     "ldpc_phys_decode_ex", "ldpc_phys_mc_run_ex", "ldpc_phys_kernel_name_ex", "ldpc_layers_build",
     "ldpc_comm_unique_id", "ldpc_comm_init", "ldpc_comm_allreduce", "ldpc_comm_barrier", "ldpc_comm_destroy",
@@ -110,6 +110,7 @@ def _declare(lib):
         "ldpc_layers_build": (ctypes.c_int, [c_i32, c_i32, P(c_i32), P(c_i32), P(c_i32), P(c_i32)]),
         "ldpc_profile_read": (ctypes.c_int, [c_vp, P(c_dbl), P(c_i64)]),
         "ldpc_rare_rows_read": (ctypes.c_int, [c_vp, P(c_i64)]),
+        "ldpc_fixed_point_read": (ctypes.c_int, [c_vp, P(c_i64)]),
         "ldpc_comm_unique_id": (ctypes.c_int, [c_vp]),
         "ldpc_comm_init": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, P(c_vp)]),
         "ldpc_comm_allreduce": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, c_u32, c_vp]),

@@ -327,6 +327,14 @@ class Decoder:
         check("ldpc_rare_rows_read", _lib.gpu().ldpc_rare_rows_read(self._h, out))
         return int(out[0]), int(out[1])
 
+    def fixed_point(self):
+        """(frames the static sub-tile decoder stopped at a bitwise fixed point,
+        frame-passes those frames did not execute) since the last call
+        (ldpc_fixed_point_read; LDPC_FIXED_POINT=0 switches the exit off)."""
+        out = (ctypes.c_int64 * 2)()
+        check("ldpc_fixed_point_read", _lib.gpu().ldpc_fixed_point_read(self._h, out))
+        return int(out[0]), int(out[1])
+
     def close(self):
         h = getattr(self, "_h", None)
         if h is not None and h.value and _lib._lib is not None and getattr(self, "_pid", None) == os.getpid():

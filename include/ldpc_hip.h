@@ -269,6 +269,64 @@ int ldpc_phys_mc_run_ex(ldpc_decoder *d_std, const ldpc_graph *g_phys, uint64_t 
 int ldpc_layers_build(int32_t m, int32_t n, const int32_t *row_ptr, const int32_t *col_idx,
                       int32_t *layer_of_row_out, int32_t *n_layers_out);
 
+/* ------------------------------- physical mode, fixed-point min-sum (q bits)
+ * What a hardware decoder computes: min-sum on saturating q-bit integer
+ * messages (csrc/phys_quant.hip).  All integer arithmetic is exact; two fp32
+ * operations happen, at the load only, and each rounds once.
+ *   qbits = q in 4..8;  llr_scale fp32, finite and > 0;
+ *   Qmax = 2^(q-1) - 1 (messages),  Pmax = 2^(q+1) - 1 (posteriors; 511 at q = 8);
+ *   load:  x = (-(float)llr[j]) * llr_scale  (lam[j] * llr_scale for on-device frames),
+ *          Lam[j] = (int)clamp(rintf(x), -Qmax, Qmax), rintf = round half to even,
+ *          the clamp in float before the conversion (non-finite input: unspecified);
+ *          L = Lam, E = 0;
+ *   check row, edges in CSR order:  Q_e = clamp(L[c_e] - E_e, -Qmax, Qmax),
+ *          a_e = |Q_e|, s_e = (Q_e < 0); min1 = smallest a, min2 = smallest over
+ *          the other edges (= min1 on a tie); mag_e = min2 at the argmin, else min1;
+ *          LDPC_CN_NMS: mag_e = (alpha_q * mag_e + 8) >> 4, alpha_q in 1..16 (sixteenths);
+ *          LDPC_CN_OMS: mag_e = max(mag_e - beta_q, 0), beta_q in 0..Qmax (quantizer steps);
+ *          R_e = (parity(all s) ^ s_e) ? -mag_e : mag_e;
+ *   LDPC_SCHED_FLOODING: every row from the same L and E, E = R, then
+ *          L[j] = clamp(Lam[j] + sum E, -Pmax, Pmax) -- an int32 sum clamped once;
+ *   LDPC_SCHED_LAYERED:  ldpc_layers_build's layers in order, per row
+ *          L[c_e] = Q_e + R_e, E_e = R_e.  |L| <= 2 Qmax < Pmax by construction:
+ *          this schedule has no posterior clamp;
+ *   exit:  after each full iteration b = (L < 0) (L == 0 is bit 0); conv = the
+ *          first iteration with H b = 0; iters, status, z = b ^ 1 and the
+ *          Monte-Carlo counters as ldpc_phys_decode / ldpc_phys_mc_run.
+ * Example (q = 6, Qmax 31, NMS alpha_q = 12): a row with L - E = [5, -3, 40, 0]
+ * has Q = [5, -3, 31, 0], min1 = 0 at edge 3, min2 = 3, magnitudes
+ * [0, 0, 0, (36 + 8) >> 4 = 2], parity 1: R = [0, 0, 0, -2].  With llr_scale 4,
+ * llr 0.625 gives Lam -2 and llr 0.875 gives Lam -4 (both ties round to even).
+ * A frame's state (int8 E, int16 L, int8 Lam) lives in LDS
+ * (ldpc_phys_q_lds_bytes; n < 65535).  With LDPC_F_PHYS_HBM, or on a graph
+ * whose quantized state does not fit, the calls return LDPC_ERANGE;
+ * LDPC_CN_SPA, a row of fewer than 2 edges, or a parameter out of range is
+ * LDPC_EINVAL.  Every check runs before any device work.  The results equal a
+ * numpy int32 restatement of these rules (tests/qminsum_ref.py).
+ * LDPC_PHYS_Q_GRID=<workgroups> in the environment (read per launch) caps the
+ * grid, so that one workgroup decodes many frames in sequence (tests, A/B). */
+/* param_q: alpha_q for LDPC_CN_NMS, beta_q for LDPC_CN_OMS.  post_out
+ * [batch][n]: the integer posterior, in units of 1 / llr_scale.  Honours
+ * LDPC_F_DEVICE_PTRS. */
+int ldpc_phys_decode_q(const ldpc_graph *g, int32_t batch, const double *llr, int32_t max_iter, uint32_t flags,
+                       int32_t cn_rule, int32_t schedule, int32_t qbits, float llr_scale, int32_t param_q,
+                       uint8_t *z_out, int32_t *conv_out, int32_t *status_out, int32_t *iters_out, int16_t *post_out,
+                       void *stream);
+/* ldpc_phys_mc_run_ex on the same on-device frames (read as fp32 Lambda rows),
+ * decoded in fixed point (same counters). */
+int ldpc_phys_mc_run_q(ldpc_decoder *d_std, const ldpc_graph *g_phys, uint64_t seed, int32_t n_points,
+                       const double *sigmas, int64_t frames_per_point, int64_t frame0, int32_t max_iter,
+                       uint32_t flags, int32_t cn_rule, int32_t schedule, int32_t qbits, float llr_scale,
+                       int32_t param_q, int64_t *counters_out, void *stream);
+/* The kernel ldpc_phys_decode_q runs: "phys_quant_reg_kernel" (flooding, on a
+ * graph the register-index kernel has a shape for) or "phys_quant_kernel" (any
+ * graph; the layered schedule; flooding with LDPC_PHYS_Q_REG=0 in the
+ * environment); "" for a combination the decode rejects. */
+const char *ldpc_phys_kernel_name_q(const ldpc_graph *g, uint32_t flags, int32_t cn_rule, int32_t schedule,
+                                    int32_t qbits);
+/* LDS bytes of a frame's quantized state under a schedule (-1: bad arguments). */
+int64_t ldpc_phys_q_lds_bytes(const ldpc_graph *g, int32_t schedule);
+
 /* ------------------------------------------------------------ profiling
  * HIP-event timing of the decoder's own launches, on the stream they are
  * launched on (used by bench.py for the live roofline).  While enabled, every

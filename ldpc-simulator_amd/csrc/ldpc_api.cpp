@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <climits>
 #include <cstdarg>
 #include <cstdio>
@@ -58,6 +59,13 @@ struct ldpc_graph {
     mutable std::string layers_err;
     mutable int *d_layers = nullptr;  // layer_ptr [n_layers + 1], then layer_rows [m]
     mutable int n_layers = 0, max_layer = 0;
+    // padded message layout of the fixed-point decoder (phys_quant.hip): built and
+    // uploaded on the graph's first quantized decode (graph_quant_tab), likewise
+    mutable std::once_flag qtab_once;
+    mutable int qtab_rc = LDPC_OK;
+    mutable std::string qtab_err;
+    mutable void *d_qtab = nullptr;  // row int2 [m], col uint16 [epad], csc int [nnz]
+    mutable ldpc::QuantTab qtab;
 };
 
 // ints ahead of the rare-row list in ldpc_decoder::rare: 4 rare-row counts, 2 x 64-bit fixed-point totals
@@ -654,6 +662,7 @@ int ldpc_graph_destroy(ldpc_graph *g) {
     (void)hipFree(g->d_ints);
     (void)hipFree(g->d_apack);
     (void)hipFree(g->d_layers);
+    (void)hipFree(g->d_qtab);
     delete g;
     return LDPC_OK;
 }
@@ -1645,6 +1654,257 @@ int ldpc_phys_mc_run_ex(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, in
                         int32_t schedule, float param, int64_t *counters_out, void *stream) {
     return phys_mc_any("ldpc_phys_mc_run_ex", d, gp, seed, n_points, sigmas, frames_per_point, frame0, max_iter, flags,
                        cn_rule, schedule, param, counters_out, stream);
+}
+
+// ------------------------------------- physical mode, fixed-point min-sum
+namespace {
+
+// Padded message bytes of a frame: every row's messages start 4-byte aligned.
+int quant_epad(const ldpc_graph *g) {
+    int64_t epad = 0;
+    for (int r = 0; r < g->dg.m; ++r) epad += (g->h_row_ptr[r + 1] - g->h_row_ptr[r] + 3) & ~3;
+    return (int)std::min<int64_t>(epad, INT_MAX / 2);
+}
+
+// Whether the quantized state of a frame fits LDS (and 16-bit column indices).
+bool quant_fits(const ldpc_graph *g, bool layered) {
+    return g->dg.n < 65535 && ldpc::phys_quant_lds_bytes(g->dg, quant_epad(g), layered) <= kLdsLimit;
+}
+
+// The argument checks of the quantized entries; they touch no device.
+int quant_check(const char *fn, const ldpc_graph *g, uint32_t flags, int32_t cn_rule, int32_t schedule, int32_t qbits,
+                float llr_scale, int32_t param_q) {
+    if (cn_rule == LDPC_CN_SPA)
+        return ldpc_fail(LDPC_EINVAL, "%s: cn_rule LDPC_CN_SPA has no fixed-point form (use LDPC_CN_NMS or "
+                                      "LDPC_CN_OMS)", fn);
+    if (cn_rule != LDPC_CN_NMS && cn_rule != LDPC_CN_OMS)
+        return ldpc_fail(LDPC_EINVAL, "%s: unknown cn_rule %d", fn, cn_rule);
+    if (schedule != LDPC_SCHED_FLOODING && schedule != LDPC_SCHED_LAYERED)
+        return ldpc_fail(LDPC_EINVAL, "%s: unknown schedule %d", fn, schedule);
+    if (qbits < 4 || qbits > 8) return ldpc_fail(LDPC_EINVAL, "%s: qbits must be in 4..8, got %d", fn, qbits);
+    if (!(llr_scale > 0.0f) || !(llr_scale <= FLT_MAX))
+        return ldpc_fail(LDPC_EINVAL, "%s: llr_scale must be finite and > 0, got %g", fn, (double)llr_scale);
+    const int qmax = (1 << (qbits - 1)) - 1;
+    if (cn_rule == LDPC_CN_NMS && (param_q < 1 || param_q > 16))
+        return ldpc_fail(LDPC_EINVAL, "%s: param_q (alpha_q, sixteenths) must be in 1..16, got %d", fn, param_q);
+    if (cn_rule == LDPC_CN_OMS && (param_q < 0 || param_q > qmax))
+        return ldpc_fail(LDPC_EINVAL, "%s: param_q (beta_q, quantizer steps) must be in 0..%d at qbits %d, got %d",
+                         fn, qmax, qbits, param_q);
+    if (g->min_row_deg < 2)
+        return ldpc_fail(LDPC_EINVAL, "%s: min-sum needs every check row to have at least 2 edges (a row has %d)",
+                         fn, g->min_row_deg);
+    if (flags & LDPC_F_PHYS_HBM)
+        return ldpc_fail(LDPC_ERANGE, "%s: the fixed-point decoder runs only with a frame's state in LDS "
+                                      "(not with LDPC_F_PHYS_HBM)", fn);
+    if (!quant_fits(g, schedule == LDPC_SCHED_LAYERED))
+        return ldpc_fail(LDPC_ERANGE, "%s: the graph's quantized state (%lld bytes, n = %d) does not fit LDS", fn,
+                         (long long)ldpc::phys_quant_lds_bytes(g->dg, quant_epad(g),
+                                                               schedule == LDPC_SCHED_LAYERED), g->dg.n);
+    return LDPC_OK;
+}
+
+// The graph's padded message layout on its device, built on the first call (any thread).
+int graph_quant_tab(const ldpc_graph *g, ldpc::QuantTab *tab) {
+    std::call_once(g->qtab_once, [g] {
+        const DevGraph &G = g->dg;
+        const int epad = quant_epad(g);
+        std::vector<int> row(2 * (size_t)G.m), csc(G.nnz), fill(G.n + 1, 0);
+        std::vector<uint16_t> col((size_t)epad, (uint16_t)G.n);  // padding: the dummy posterior L[n]
+        for (int e = 0; e < G.nnz; ++e) fill[g->h_col_idx[e] + 1]++;
+        for (int j = 0; j < G.n; ++j) fill[j + 1] += fill[j];  // = csc_ptr; rows ascending within a column below
+        int off = 0;
+        for (int r = 0; r < G.m; ++r) {
+            const int b = g->h_row_ptr[r], deg = g->h_row_ptr[r + 1] - b;
+            row[2 * (size_t)r] = off;
+            row[2 * (size_t)r + 1] = deg;
+            for (int i = 0; i < deg; ++i) {
+                const int c = g->h_col_idx[b + i];
+                col[off + i] = (uint16_t)c;
+                csc[fill[c]++] = off + i;
+            }
+            off += (deg + 3) & ~3;
+        }
+        // the column table right after the rows: it is read 8 bytes at a time (hipMalloc aligns to 256
+        // bytes, row_bytes is a multiple of 8 and a row's slots start at a multiple of 4)
+        const size_t row_bytes = sizeof(int) * row.size(), col_bytes = sizeof(uint16_t) * col.size();
+        char *d = nullptr;
+        hipError_t e = hipMalloc((void **)&d, row_bytes + col_bytes + sizeof(int) * csc.size());
+        if (e == hipSuccess) e = hipMemcpy(d, row.data(), row_bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d + row_bytes, col.data(), col_bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess)
+            e = hipMemcpy(d + row_bytes + col_bytes, csc.data(), sizeof(int) * csc.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            g->qtab_rc = LDPC_EDEVICE;
+            g->qtab_err = std::string("quantized layout upload failed: ") + hipGetErrorString(e);
+            return;
+        }
+        g->d_qtab = d;
+        g->qtab.row = reinterpret_cast<const int2 *>(d);
+        g->qtab.col = reinterpret_cast<const uint16_t *>(d + row_bytes);
+        g->qtab.csc = reinterpret_cast<const int *>(d + row_bytes + col_bytes);
+        g->qtab.epad = epad;
+    });
+    if (g->qtab_rc) return ldpc_fail(g->qtab_rc, "%s", g->qtab_err.c_str());
+    *tab = g->qtab;
+    return LDPC_OK;
+}
+
+// Fill the kernel's rule (device tables: call with g's device current, after quant_check).
+int quant_rule(const ldpc_graph *g, int32_t cn_rule, int32_t schedule, int32_t qbits, float llr_scale,
+               int32_t param_q, ldpc::QuantRule *rule) {
+    *rule = ldpc::QuantRule{};
+    rule->cn = cn_rule;
+    rule->qbits = qbits;
+    rule->scale = llr_scale;
+    rule->param_q = param_q;
+    if (int rc = graph_quant_tab(g, &rule->tab)) return rc;
+    if (schedule == LDPC_SCHED_LAYERED) {
+        PhysRule pr;
+        if (int rc = graph_layers(g, &pr)) return rc;
+        rule->layer_ptr = pr.layer_ptr;
+        rule->layer_rows = pr.layer_rows;
+        rule->n_layers = pr.n_layers;
+        rule->max_layer = pr.max_layer;
+    }
+    return LDPC_OK;
+}
+
+// LDPC_PHYS_Q_GRID=<workgroups> (read per launch) caps the grid launch_phys_quant
+// picks (the workgroups the device holds at once): one workgroup then decodes
+// many frames in sequence (tests of LDS reuse, A/B).
+int phys_quant_max_grid() {
+    if (const char *e = getenv("LDPC_PHYS_Q_GRID")) {
+        const int cap = atoi(e);
+        if (cap > 0) return cap;
+    }
+    return INT_MAX;
+}
+
+}  // namespace
+
+const char *ldpc_phys_kernel_name_q(const ldpc_graph *g, uint32_t flags, int32_t cn_rule, int32_t schedule,
+                                    int32_t qbits) {
+    if (!g || (cn_rule != LDPC_CN_NMS && cn_rule != LDPC_CN_OMS) ||
+        (schedule != LDPC_SCHED_FLOODING && schedule != LDPC_SCHED_LAYERED) || qbits < 4 || qbits > 8 ||
+        g->min_row_deg < 2 || (flags & LDPC_F_PHYS_HBM) || !quant_fits(g, schedule == LDPC_SCHED_LAYERED))
+        return "";
+    const bool layered = schedule == LDPC_SCHED_LAYERED;
+    return ldpc::phys_quant_reg_shape(g->dg, quant_epad(g), layered) >= 0 ? "phys_quant_reg_kernel" : "phys_quant_kernel";
+}
+
+int64_t ldpc_phys_q_lds_bytes(const ldpc_graph *g, int32_t schedule) {
+    if (!g || (schedule != LDPC_SCHED_FLOODING && schedule != LDPC_SCHED_LAYERED)) return -1;
+    return (int64_t)ldpc::phys_quant_lds_bytes(g->dg, quant_epad(g), schedule == LDPC_SCHED_LAYERED);
+}
+
+int ldpc_phys_decode_q(const ldpc_graph *g, int32_t batch, const double *llr, int32_t max_iter, uint32_t flags,
+                       int32_t cn_rule, int32_t schedule, int32_t qbits, float llr_scale, int32_t param_q,
+                       uint8_t *z_out, int32_t *conv_out, int32_t *status_out, int32_t *iters_out, int16_t *post_out,
+                       void *stream) {
+    const char *fn = "ldpc_phys_decode_q";
+    if (!g) return ldpc_fail(LDPC_EINVAL, "%s: NULL graph", fn);
+    if (batch < 0 || max_iter < 1 || (batch > 0 && !llr))
+        return ldpc_fail(LDPC_EINVAL, "%s: bad arguments (batch=%d max_iter=%d)", fn, batch, max_iter);
+    if (int rc = quant_check(fn, g, flags, cn_rule, schedule, qbits, llr_scale, param_q)) return rc;
+    if (batch == 0) return LDPC_OK;
+    DeviceGuard dg(g->device);
+    ldpc::QuantRule rule;
+    if (int rc = quant_rule(g, cn_rule, schedule, qbits, llr_scale, param_q, &rule)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const DevGraph &G = g->dg;
+    const size_t n = (size_t)G.n, B = (size_t)batch;
+    auto launch = [&](const double *in, uint8_t *z, int *conv, int *status, int *iters, int16_t *post) {
+        return ldpc::launch_phys_quant(G, in, nullptr, batch, max_iter, z, conv, status, iters, post, nullptr, nullptr,
+                                       phys_quant_max_grid(), s, rule);
+    };
+    if (flags & LDPC_F_DEVICE_PTRS) {
+        HIP_TRY(launch(llr, z_out, conv_out, status_out, iters_out, post_out));
+        return LDPC_OK;
+    }
+    double *d_llr = nullptr;
+    uint8_t *d_z = nullptr;
+    int *d_i = nullptr;
+    int16_t *d_post = nullptr;
+    int rc = dev_alloc(&d_llr, B * n);
+    if (!rc) rc = dev_alloc(&d_z, B * n);
+    if (!rc) rc = dev_alloc(&d_i, 3 * B);
+    if (!rc && post_out) rc = dev_alloc(&d_post, B * n);
+    hipError_t e = hipSuccess;
+    if (!rc) {
+        e = hipMemcpyAsync(d_llr, llr, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
+        if (!e) e = launch(d_llr, d_z, d_i, d_i + B, d_i + 2 * B, d_post);
+        if (!e && z_out) e = hipMemcpyAsync(z_out, d_z, B * n, hipMemcpyDeviceToHost, s);
+        if (!e && conv_out) e = hipMemcpyAsync(conv_out, d_i, sizeof(int) * B, hipMemcpyDeviceToHost, s);
+        if (!e && status_out) e = hipMemcpyAsync(status_out, d_i + B, sizeof(int) * B, hipMemcpyDeviceToHost, s);
+        if (!e && iters_out) e = hipMemcpyAsync(iters_out, d_i + 2 * B, sizeof(int) * B, hipMemcpyDeviceToHost, s);
+        if (!e && post_out) e = hipMemcpyAsync(post_out, d_post, sizeof(int16_t) * B * n, hipMemcpyDeviceToHost, s);
+        if (!e) e = hipStreamSynchronize(s);
+        if (e) rc = ldpc_fail(LDPC_EDEVICE, "%s: %s", fn, hipGetErrorString(e));
+    }
+    (void)hipFree(d_llr);
+    (void)hipFree(d_z);
+    (void)hipFree(d_i);
+    (void)hipFree(d_post);
+    return rc;
+}
+
+int ldpc_phys_mc_run_q(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int32_t n_points, const double *sigmas,
+                       int64_t frames_per_point, int64_t frame0, int32_t max_iter, uint32_t flags, int32_t cn_rule,
+                       int32_t schedule, int32_t qbits, float llr_scale, int32_t param_q, int64_t *counters_out,
+                       void *stream) {
+    const char *fn = "ldpc_phys_mc_run_q";
+    if (!gp) return ldpc_fail(LDPC_EINVAL, "%s: NULL graph", fn);
+    if (!d || n_points <= 0 || !sigmas || frames_per_point < 0 || frame0 < 0 || max_iter < 1 || !counters_out)
+        return ldpc_fail(LDPC_EINVAL, "%s: bad arguments", fn);
+    const DevGraph &G = d->g->dg;
+    const DevGraph &P = gp->dg;
+    if (!G.std_form && !(G.ira && d->g == gp))
+        return ldpc_fail(LDPC_EINVAL,
+                         "%s: the decoder's graph must be the code's H_std = [A | I_m], or the "
+                         "IRA graph itself", fn);
+    if (P.n != G.n || P.k != G.k)
+        return ldpc_fail(LDPC_EINVAL, "%s: physical graph shape %dx%d != %dx%d", fn, P.m, P.n, G.m, G.n);
+    for (int p = 0; p < n_points; ++p)
+        if (!(sigmas[p] > 0.0)) return ldpc_fail(LDPC_EINVAL, "%s: sigma[%d] <= 0", fn, p);
+    if (int rc = quant_check(fn, gp, flags, cn_rule, schedule, qbits, llr_scale, param_q)) return rc;
+    DeviceGuard dg(d->g->device);
+    ldpc::QuantRule rule;
+    if (int rc = quant_rule(gp, cn_rule, schedule, qbits, llr_scale, param_q, &rule)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = ensure_pbits(d, G)) return rc;
+    const int need = n_points * LDPC_MC_NCOUNT;
+    if (d->counters_cap < need) {
+        (void)hipFree(d->counters);
+        d->counters = nullptr;
+        d->counters_cap = 0;
+        if (int rc = dev_alloc(&d->counters, (size_t)need + 1)) return rc;
+        d->counters_cap = need;
+    }
+    HIP_TRY(hipMemsetAsync(d->counters, 0, sizeof(unsigned long long) * need, s));
+    const int64_t cap = (int64_t)d->cap_tiles * kTile;
+    for (int p = 0; p < n_points; ++p) {
+        unsigned long long *ctr = d->counters + (size_t)p * LDPC_MC_NCOUNT;
+        for (int64_t start = 0; start < frames_per_point; start += cap) {
+            const int cnt = (int)std::min<int64_t>(cap, frames_per_point - start);
+            state_bind(d, (cnt + kTile - 1) / kTile, cnt);
+            const DevState st = d->st;
+            float *rows = (float *)d->llr_stage;  // the frames as fp32 Lambda rows, as phys_mc_any's LDS path
+            HIP_TRY(timed(d, LDPC_K_GEN, s, [&] {
+                return ldpc::launch_frames(G, st, phys_tile(d), seed, p, sigmas[p], frame0 + start,
+                                           ldpc::kFramesRowLambda, rows, s);
+            }));
+            HIP_TRY(timed(d, LDPC_K_PHYS, s, [&] {
+                return ldpc::launch_phys_quant(P, nullptr, rows, cnt, max_iter, nullptr, nullptr, nullptr, nullptr,
+                                               nullptr, st.ubits, ctr, phys_quant_max_grid(), s, rule);
+            }));
+        }
+    }
+    std::vector<unsigned long long> h(need);
+    HIP_TRY(hipMemcpyAsync(h.data(), d->counters, sizeof(unsigned long long) * need, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int i = 0; i < need; ++i) counters_out[i] = (int64_t)h[i];
+    return LDPC_OK;
 }
 
 // -------------------------------------------------------------- profiling

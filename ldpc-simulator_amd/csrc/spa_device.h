@@ -225,6 +225,37 @@ hipError_t launch_phys_layered(const DevGraph &g, const double *llr, const float
                                const uint32_t *ubits, unsigned long long *ctr, int grid, hipStream_t s,
                                const PhysRule &rule);
 
+// fixed-point min-sum with q-bit messages (phys_quant.hip): int8 E, int16 L and
+// (flooding) int8 Lam of a frame in LDS.  QuantTab is the graph's padded message
+// layout on the device (ldpc_api.cpp builds it on first use): row r's messages
+// are the deg bytes at the 4-byte aligned offset row[r].x.
+struct QuantTab {
+    const int2 *row = nullptr;      // [m] {padded byte offset of the row's messages, its degree}
+    const uint16_t *col = nullptr;  // [epad] column of each padded slot (n in the padding)
+    const int *csc = nullptr;       // [nnz] padded offset of CSC position p (DevGraph::csc_ptr order)
+    int epad = 0;                   // padded message bytes of a frame (a multiple of 4)
+};
+struct QuantRule {
+    int cn = kCnNms;                // kCnNms or kCnOms
+    int qbits = 6;                  // 4..8
+    float scale = 4.0f;             // llr_scale
+    int param_q = 12;               // alpha_q (kCnNms, 1..16) or beta_q (kCnOms, 0..Qmax)
+    const int *layer_ptr = nullptr;  // as PhysRule; null: flooding
+    const int *layer_rows = nullptr;
+    int n_layers = 0;
+    int max_layer = 0;
+    QuantTab tab;
+};
+size_t phys_quant_lds_bytes(const DevGraph &g, int epad, bool layered);
+// >= 0: the flooding decoder runs phys_quant_reg_kernel (indices in registers), else phys_quant_kernel
+int phys_quant_reg_shape(const DevGraph &g, int epad, bool layered);
+int phys_quant_threads(const DevGraph &g, const QuantRule &rule);
+// llr [count][n] fp64, or lam [count][n] fp32 Lambda (then llr is ignored).  The grid is the workgroups
+// the device holds at once (CUs x resident per CU), at most max_grid and count.
+hipError_t launch_phys_quant(const DevGraph &g, const double *llr, const float *lam, int count, int max_iter,
+                             uint8_t *z, int *conv, int *status, int *iters, int16_t *post, const uint32_t *ubits,
+                             unsigned long long *ctr, int max_grid, hipStream_t s, const QuantRule &rule);
+
 // physical mode, HBM-resident tiles + IRA frame source (phys_tile.hip)
 // on-device frames of a chunk (frame_kernels.hip): info bits -> st.ubits,
 // parities via pt.pbits/pt.wpar (H_std [A|I] or IRA graph), channel LLRs as

@@ -46,6 +46,7 @@ EXPORTED = (
     "ldpc_profile_enable", "ldpc_profile_read", "ldpc_rare_rows_read", "ldpc_fixed_point_read",
     "ldpc_phys_lds_bytes", "ldpc_phys_decode", "ldpc_phys_mc_run",
     "ldpc_phys_decode_ex", "ldpc_phys_mc_run_ex", "ldpc_phys_kernel_name_ex", "ldpc_layers_build",
+    "ldpc_phys_decode_q", "ldpc_phys_mc_run_q", "ldpc_phys_kernel_name_q", "ldpc_phys_q_lds_bytes",
     "ldpc_comm_unique_id", "ldpc_comm_init", "ldpc_comm_allreduce", "ldpc_comm_barrier", "ldpc_comm_destroy",
     "ldpc_device_synchronize",
 )
@@ -107,6 +108,12 @@ def _declare(lib):
         "ldpc_phys_mc_run_ex": (ctypes.c_int, [c_vp, c_vp, c_u64, c_i32, P(c_dbl), c_i64, c_i64, c_i32, c_u32,
                                                c_i32, c_i32, c_flt, P(c_i64), c_vp]),
         "ldpc_phys_kernel_name_ex": (ctypes.c_char_p, [c_vp, c_u32, c_i32, c_i32]),
+        "ldpc_phys_decode_q": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32, c_u32, c_i32, c_i32, c_i32, c_flt, c_i32, c_vp,
+                                              c_vp, c_vp, c_vp, c_vp, c_vp]),
+        "ldpc_phys_mc_run_q": (ctypes.c_int, [c_vp, c_vp, c_u64, c_i32, P(c_dbl), c_i64, c_i64, c_i32, c_u32,
+                                              c_i32, c_i32, c_i32, c_flt, c_i32, P(c_i64), c_vp]),
+        "ldpc_phys_kernel_name_q": (ctypes.c_char_p, [c_vp, c_u32, c_i32, c_i32, c_i32]),
+        "ldpc_phys_q_lds_bytes": (c_i64, [c_vp, c_i32]),
         "ldpc_layers_build": (ctypes.c_int, [c_i32, c_i32, P(c_i32), P(c_i32), P(c_i32), P(c_i32)]),
         "ldpc_profile_read": (ctypes.c_int, [c_vp, P(c_dbl), P(c_i64)]),
         "ldpc_rare_rows_read": (ctypes.c_int, [c_vp, P(c_i64)]),

@@ -127,22 +127,60 @@ def phys_rule_args(cn="spa", schedule="flooding", alpha=0.75, beta=0.5):
     return CN_RULES[cn], SCHEDULES[schedule], {"spa": 0.0, "nms": alpha, "oms": beta}[cn]
 
 
-def phys_kernel_name(graph, hbm=False, cn="spa", schedule="flooding"):
+def phys_quant_args(cn, alpha=0.75, beta=0.5, qbits=6, llr_scale=4.0):
+    """(qbits, llr_scale, param_q) of the fixed-point entries (ldpc_phys_decode_q):
+    qbits in 4..8, llr_scale finite and > 0, and the float alpha / beta as the
+    integers the decoder computes with -- alpha_q = round(16 alpha) in 1..16
+    (sixteenths) for "nms", beta_q = round(beta llr_scale) in 0..Qmax (quantizer
+    steps, Qmax = 2^(qbits-1) - 1) for "oms".  Raises ValueError otherwise --
+    before any device call."""
+    if cn not in ("nms", "oms"):
+        raise ValueError(f"qbits needs a min-sum rule (cn='nms' or 'oms'), got cn={cn!r}")
+    if isinstance(qbits, bool) or int(qbits) != qbits or not 4 <= int(qbits) <= 8:
+        raise ValueError(f"qbits must be an integer in 4..8, got {qbits!r}")
+    qbits, llr_scale = int(qbits), float(llr_scale)
+    if not (np.isfinite(llr_scale) and llr_scale > 0.0 and np.isfinite(np.float32(llr_scale))
+            and np.float32(llr_scale) > 0.0):
+        raise ValueError(f"llr_scale must be finite and > 0 (in fp32), got {llr_scale}")
+    qmax = (1 << (qbits - 1)) - 1
+    if cn == "nms":
+        param_q = int(round(16.0 * float(alpha)))
+        if not 1 <= param_q <= 16:
+            raise ValueError(f"alpha = {alpha} gives alpha_q = round(16 alpha) = {param_q}, outside 1..16")
+    else:
+        param_q = int(round(float(beta) * llr_scale))
+        if not 0 <= param_q <= qmax:
+            raise ValueError(f"beta = {beta} gives beta_q = round(beta llr_scale) = {param_q}, outside 0..{qmax} "
+                             f"(Qmax at qbits = {qbits})")
+    return qbits, llr_scale, param_q
+
+
+def phys_kernel_name(graph, hbm=False, cn="spa", schedule="flooding", qbits=None, llr_scale=4.0):
     """Measurement label: the kernel phys_decode runs for these options."""
     rule, sched, _ = phys_rule_args(cn, schedule)
+    if qbits is not None:
+        qbits, _, _ = phys_quant_args(cn, qbits=qbits, llr_scale=llr_scale)
+        return _lib.gpu().ldpc_phys_kernel_name_q(graph.handle, LDPC_F_PHYS_HBM if hbm else 0, rule, sched,
+                                                  qbits).decode()
     return _lib.gpu().ldpc_phys_kernel_name_ex(graph.handle, LDPC_F_PHYS_HBM if hbm else 0, rule, sched).decode()
 
 
 def phys_decode(graph, llr, max_iter, post=False, hbm=False, cn="spa", schedule="flooding", alpha=0.75, beta=0.5,
-                ex=False):
+                ex=False, qbits=None, llr_scale=4.0):
     """Physical-mode decode of [B, n] LLRs on a sparse graph (H[:, perm]).
 
     State in LDS when a frame fits, else in HBM (hbm=True forces HBM).
     cn / schedule / alpha / beta: phys_rule_args; the defaults are the
     sum-product flooding decoder (ldpc_phys_decode), anything else goes through
     ldpc_phys_decode_ex (ex=True: the defaults too -- the library takes the
-    same path for them either way; tests).  Layered runs on the LDS path only."""
+    same path for them either way; tests).  Layered runs on the LDS path only.
+    qbits=4..8: the fixed-point min-sum decoder (ldpc_phys_decode_q;
+    phys_quant_args turns alpha / beta into its integers) on LLRs scaled by
+    llr_scale; post is then the integer posterior, int16, in units of
+    1 / llr_scale.  qbits=None: the fp32 decoders, llr_scale unused."""
     rule, sched, param = phys_rule_args(cn, schedule, alpha, beta)
+    if qbits is not None:
+        qbits, llr_scale, param_q = phys_quant_args(cn, alpha, beta, qbits, llr_scale)
     llr = np.ascontiguousarray(np.atleast_2d(np.asarray(llr, dtype=np.float64)))
     B, n = llr.shape
     if n != graph.n:
@@ -151,9 +189,13 @@ def phys_decode(graph, llr, max_iter, post=False, hbm=False, cn="spa", schedule=
     conv = np.empty(B, np.int32)
     status = np.empty(B, np.int32)
     iters = np.empty(B, np.int32)
-    Lp = np.empty((B, n), np.float32) if post else None
+    Lp = np.empty((B, n), np.float32 if qbits is None else np.int16) if post else None
     flags = LDPC_F_PHYS_HBM if hbm else 0
-    if (cn, schedule) == ("spa", "flooding") and not ex:
+    if qbits is not None:
+        check("ldpc_phys_decode_q", _lib.gpu().ldpc_phys_decode_q(
+            graph.handle, B, _lib.ptr(llr), int(max_iter), flags, rule, sched, qbits, llr_scale, param_q,
+            _lib.ptr(z), _lib.ptr(conv), _lib.ptr(status), _lib.ptr(iters), _lib.ptr(Lp), None))
+    elif (cn, schedule) == ("spa", "flooding") and not ex:
         check("ldpc_phys_decode", _lib.gpu().ldpc_phys_decode(
             graph.handle, B, _lib.ptr(llr), int(max_iter), flags, _lib.ptr(z), _lib.ptr(conv), _lib.ptr(status),
             _lib.ptr(iters), _lib.ptr(Lp), None))
@@ -288,20 +330,26 @@ class Decoder:
         return out
 
     def phys_mc_run(self, phys_graph, seed, sigmas, frames_per_point, frame0, max_iter, hbm=False, cn="spa",
-                    schedule="flooding", alpha=0.75, beta=0.5):
+                    schedule="flooding", alpha=0.75, beta=0.5, qbits=None, llr_scale=4.0):
         """Physical mode (§8 f4): same on-device frames, decoded on the sparse graph.
 
         This decoder's graph is the code's H_std (frame source) or, for an IRA
         code, phys_graph itself.  hbm=True forces the HBM-resident tile path.
         cn / schedule / alpha / beta as phys_decode (the defaults are
-        ldpc_phys_mc_run, anything else ldpc_phys_mc_run_ex)."""
+        ldpc_phys_mc_run, anything else ldpc_phys_mc_run_ex); qbits /
+        llr_scale as phys_decode (ldpc_phys_mc_run_q)."""
         rule, sched, param = phys_rule_args(cn, schedule, alpha, beta)
+        if qbits is not None:
+            qbits, llr_scale, param_q = phys_quant_args(cn, alpha, beta, qbits, llr_scale)
         sig = np.ascontiguousarray(np.asarray(sigmas, dtype=np.float64))
         out = np.zeros((len(sig), LDPC_MC_NCOUNT), np.int64)
         head = (self._h, phys_graph.handle, int(seed), len(sig), sig.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
                 int(frames_per_point), int(frame0), int(max_iter), LDPC_F_PHYS_HBM if hbm else 0)
         tail = (out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), None)
-        if (cn, schedule) == ("spa", "flooding"):
+        if qbits is not None:
+            check("ldpc_phys_mc_run_q", _lib.gpu().ldpc_phys_mc_run_q(*head, rule, sched, qbits, llr_scale, param_q,
+                                                                      *tail))
+        elif (cn, schedule) == ("spa", "flooding"):
             check("ldpc_phys_mc_run", _lib.gpu().ldpc_phys_mc_run(*head, *tail))
         else:
             check("ldpc_phys_mc_run_ex", _lib.gpu().ldpc_phys_mc_run_ex(*head, rule, sched, param, *tail))

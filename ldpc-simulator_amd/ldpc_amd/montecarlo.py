@@ -94,27 +94,35 @@ def run_sweep(decoder, snrs, blocks, max_iter, seed=20260213, nllr=False, speed=
 DECODER_TYPES = {"spa": "sumproduct", "nms": "minsum-normalized", "oms": "minsum-offset"}
 
 
-def decoder_type(cn_rule="spa", schedule="flooding"):
-    """The result schema's decoder_type for a check rule and schedule."""
-    return DECODER_TYPES[cn_rule] + ("-layered" if schedule == "layered" else "")
+def decoder_type(cn_rule="spa", schedule="flooding", qbits=None):
+    """The result schema's decoder_type for a check rule, a schedule and (fixed
+    point) the message width, e.g. "minsum-normalized-layered-q6"."""
+    return (DECODER_TYPES[cn_rule] + ("-layered" if schedule == "layered" else "")
+            + (f"-q{int(qbits)}" if qbits is not None else ""))
 
 
 def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65536, device=0,
              rank=0, world=1, allreduce=None, matrix_path="", mode="parity", cn_rule="spa", schedule="flooding",
-             alpha=0.75, beta=0.5):
+             alpha=0.75, beta=0.5, qbits=None, llr_scale=4.0):
     """Full sweep on this process's GPU -> SimulationResult (reference schema).
 
     mode "parity" is the reference's decoder on H_std; "physical" decodes the
     same on-device frames on the sparse graph (Decoder.phys_mc_run) with the
     check rule cn_rule ("spa", "nms", "oms"; alpha / beta) and the schedule
-    ("flooding", "layered") -- those options need mode="physical"."""
+    ("flooding", "layered") -- those options need mode="physical".  qbits
+    (4..8) selects the fixed-point min-sum decoder on LLRs scaled by llr_scale
+    (device.phys_quant_args); it needs mode="physical" and a min-sum rule."""
     from .code import EncoderDecoderData, load_committed_code
-    from .device import Decoder, Graph, phys_rule_args
+    from .device import Decoder, Graph, phys_quant_args, phys_rule_args
     if mode not in ("parity", "physical"):
         raise ValueError(f"mode must be 'parity' or 'physical', got {mode!r}")
     phys_rule_args(cn_rule, schedule, alpha, beta)  # ValueError before any device call
     if mode == "parity" and (cn_rule, schedule) != ("spa", "flooding"):
         raise ValueError("cn_rule / schedule need mode='physical' (parity mode is the reference's sum-product)")
+    if qbits is not None:
+        if mode != "physical":
+            raise ValueError("qbits needs mode='physical'")
+        phys_quant_args(cn_rule, alpha, beta, qbits, llr_scale)
     t0 = time.time()
     if isinstance(matrix, EncoderDecoderData):
         edd = matrix
@@ -130,14 +138,14 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
 
         def counter_fn(sigmas, cnt, frame0):
             return dec.phys_mc_run(gp, seed, sigmas, cnt, frame0, max_iter, cn=cn_rule, schedule=schedule,
-                                   alpha=alpha, beta=beta)
+                                   alpha=alpha, beta=beta, qbits=qbits, llr_scale=llr_scale)
     ctr = run_sweep(dec, snrs, blocks, max_iter, seed=seed, nllr=nllr, rank=rank, world=world,
                     allreduce=allreduce, counter_fn=counter_fn)
     pts = point_results(ctr, edd._k, snrs, matrix_path=matrix_path or str(matrix), max_iter=max_iter)
     cfg = SimulationConfig(
         matrix_path=matrix_path or str(matrix), n=edd._n, m=edd._m, k=edd._k, rate=edd._rate,
         blocks=int(blocks), max_iterations=int(max_iter), encoding_method="standard",
-        interleaver_type="none", decoder_type=decoder_type(cn_rule, schedule), channel_mode=1, modulation=1,
+        interleaver_type="none", decoder_type=decoder_type(cn_rule, schedule, qbits), channel_mode=1, modulation=1,
         speed=1.0, snr_range=(snrs[0], snrs[-1], (snrs[1] - snrs[0]) if len(snrs) > 1 else 0.0),
         threads=world, timestamp=datetime.now().isoformat())
     return SimulationResult(config=cfg, snr_points=pts, wall_clock_seconds=time.time() - t0), ctr
@@ -163,22 +171,33 @@ def build_parser():
                     help="physical mode: layered needs a min-sum rule")
     ap.add_argument("--alpha", type=float, default=None, help="normalized min-sum factor in (0, 1] (default 0.75)")
     ap.add_argument("--beta", type=float, default=None, help="offset min-sum offset >= 0 (default 0.5)")
+    ap.add_argument("--qbits", type=int, default=None,
+                    help="physical mode, min-sum rules: fixed-point decoder with messages of 4..8 bits")
+    ap.add_argument("--llr-scale", type=float, default=None,
+                    help="with --qbits: quantizer steps per unit of LLR (default 4)")
     return ap
 
 
 def parse_args(argv=None):
     """Parse the command line; the physical-mode options without --mode physical,
     and combinations the decoder rejects, are argparse errors."""
-    from .device import phys_rule_args
+    from .device import phys_quant_args, phys_rule_args
     ap = build_parser()
     a = ap.parse_args(argv)
     if a.mode != "physical" and (a.cn_rule != "spa" or a.schedule != "flooding" or a.alpha is not None
                                  or a.beta is not None):
         ap.error("--cn-rule, --schedule, --alpha and --beta need --mode physical")
+    if a.mode != "physical" and (a.qbits is not None or a.llr_scale is not None):
+        ap.error("--qbits and --llr-scale need --mode physical")
+    if a.llr_scale is not None and a.qbits is None:
+        ap.error("--llr-scale needs --qbits")
+    a.llr_scale = 4.0 if a.llr_scale is None else a.llr_scale
     a.alpha = 0.75 if a.alpha is None else a.alpha
     a.beta = 0.5 if a.beta is None else a.beta
     try:
         phys_rule_args(a.cn_rule, a.schedule, a.alpha, a.beta)
+        if a.qbits is not None:
+            phys_quant_args(a.cn_rule, a.alpha, a.beta, a.qbits, a.llr_scale)
     except ValueError as e:
         ap.error(str(e))
     return a
@@ -197,7 +216,7 @@ def main(argv=None):
     snrs = snr_grid(a.initial_snr, a.end_snr, a.step_snr)
     res, _ = simulate(a.matrix, snrs, a.blocks, a.iterations, seed=a.seed, nllr=a.normalized_llr,
                       device=local, rank=rank, world=world, allreduce=allreduce, mode=a.mode, cn_rule=a.cn_rule,
-                      schedule=a.schedule, alpha=a.alpha, beta=a.beta)
+                      schedule=a.schedule, alpha=a.alpha, beta=a.beta, qbits=a.qbits, llr_scale=a.llr_scale)
     if rank == 0:
         for sp in res.snr_points:
             print(f"SNR {sp.snr_db:.2f} dB  FER {sp.fer:.6f}  BER {sp.ber:.6e}  "

@@ -4,14 +4,18 @@
 wimax_2304_0.5 (or --code), the project's on-device frame source, the two SNR
 points bench.py uses for physical mode (-2.5 dB in the waterfall, 1.0 dB), a
 step of --frames frames at --iters max iterations per configuration:
-sum-product flooding, normalized min-sum flooding, normalized min-sum layered.
+sum-product flooding, normalized min-sum flooding, normalized min-sum layered,
+and (--qbits, default 6; 0 skips them) the fixed-point normalized min-sum
+decoder under both schedules on the same frames, in each point's "quantized"
+rows.
 Every timed step runs under ldpc_profile_enable.  Prints ONE JSON line: per
 SNR and configuration the kernel name, codewords/s (wall clock of the timed
 steps), FER, average iterations and the decode kernel's milliseconds per
 frame-iteration (LDPC_K_PHYS event time / counter slot 6).
 
 The yardstick is the sum-product flooding row of the same run on the same
-GPU -- that kernel is untouched by the min-sum work.  LDPC_LAYERED_NT and
+GPU -- that kernel is untouched by the min-sum work; the yardstick of a
+quantized row is the fp32 min-sum row of the same schedule.  LDPC_LAYERED_NT and
 LDPC_LAYERED_PER_CU (read by the library per launch) override the layered
 kernel's block size and workgroups per CU for A/B runs of this tool.
 """
@@ -39,6 +43,8 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--configs", nargs="+", default=["-".join(c) for c in CONFIGS],
                     choices=["-".join(c) for c in CONFIGS], help="rule-schedule pairs to run")
+    ap.add_argument("--qbits", type=int, default=6, help="message bits of the quantized rows (0: none)")
+    ap.add_argument("--llr-scale", type=float, default=4.0, help="quantizer steps per unit of LLR")
     a = ap.parse_args(argv)
 
     import numpy as np
@@ -55,9 +61,12 @@ def main(argv=None):
     points = []
     for snr in a.snrs:
         sig = mc.sigma_for_snr(snr)
-        rows = []
-        for cn, schedule in (c.split("-") for c in a.configs):
-            kw = dict(cn=cn, schedule=schedule, alpha=a.alpha)
+        rows, qrows = [], []
+        runs = [(c.split("-"), {}) for c in a.configs]
+        if a.qbits:
+            runs += [(("nms", sch), dict(qbits=a.qbits, llr_scale=a.llr_scale)) for sch in ("flooding", "layered")]
+        for (cn, schedule), q in runs:
+            kw = dict(cn=cn, schedule=schedule, alpha=a.alpha, **q)
             dec.phys_mc_run(pg, SEED, [sig], B, 0, a.iters, **kw)  # warm-up (builds the layer table)
             dec.profile_read()
             dec.profile(True)
@@ -69,14 +78,15 @@ def main(argv=None):
             dec.profile(False)
             pms, launches = dec.profile_read()["phys"]
             frames = int(tot[0])
-            rows.append({"cn": cn, "schedule": schedule, "kernel": phys_kernel_name(pg, cn=cn, schedule=schedule),
-                         "cw_per_s": frames / dt, "fer": int(tot[1]) / frames, "avg_iters": int(tot[6]) / frames,
-                         "kernel_ms": pms, "launches": int(launches),
-                         "kernel_ms_per_frame_iteration": pms / max(int(tot[6]), 1)})
-        points.append({"snr_db": snr, "configs": rows})
+            (qrows if q else rows).append({
+                "cn": cn, "schedule": schedule, **q, "kernel": phys_kernel_name(pg, cn=cn, schedule=schedule, **q),
+                "cw_per_s": frames / dt, "fer": int(tot[1]) / frames, "avg_iters": int(tot[6]) / frames,
+                "kernel_ms": pms, "launches": int(launches),
+                "kernel_ms_per_frame_iteration": pms / max(int(tot[6]), 1)})
+        points.append({"snr_db": snr, "configs": rows, **({"quantized": qrows} if qrows else {})})
     dec.close()
     print(json.dumps({"tool": "bench_phys_rules", "code": a.code, "frames_per_step": B, "steps": a.steps,
-                      "max_iter": a.iters, "alpha": a.alpha, "points": points}))
+                      "max_iter": a.iters, "alpha": a.alpha, "points": points}))  # quantized rows: alpha_q = round(16 alpha)
 
 
 if __name__ == "__main__":

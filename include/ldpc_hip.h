@@ -203,10 +203,16 @@ int ldpc_mc_run(ldpc_decoder *d, uint64_t seed, int32_t n_points, const double *
  * rule (Lambda = -llr), fp32.  A frame's state lives in LDS (one workgroup per
  * frame) when it fits (ldpc_phys_lds_bytes <= ~159 KB), otherwise -- or with
  * LDPC_F_PHYS_HBM -- in HBM, 64 frames per tile (csrc/phys_tile.hip); both
- * paths compute bit-identical results.  Inputs/outputs keep the reference's
- * conventions: llr as produced by channel.py, z = (bit estimate) ^ 1,
+ * paths compute bit-identical results, on any graph ldpc_graph_create accepts
+ * (a column without edges keeps L = Lambda on both).  Inputs/outputs keep the
+ * reference's conventions: llr as produced by channel.py, z = (bit estimate) ^ 1,
  * status 0 = OK.  The HBM path of ldpc_phys_decode synchronises before it
  * returns (it uses a temporary workspace), also with LDPC_F_DEVICE_PTRS.
+ * The LDS path runs phys_reg_kernel (a thread's rows and columns in registers)
+ * on the graphs whose shape it has, else the generic phys_kernel, with the same
+ * operations in the same order: bit-identical.  LDPC_PHYS_REG=0 in the
+ * environment (read per launch, as LDPC_PHYS_Q_REG) forces the generic kernel
+ * (tests, A/B); ldpc_phys_kernel_name* follow it.
  */
 int64_t ldpc_phys_lds_bytes(const ldpc_graph *g);
 int ldpc_phys_decode(const ldpc_graph *g, int32_t batch, const double *llr, int32_t max_iter, uint32_t flags,

@@ -251,7 +251,8 @@ size_t phys_lds_bytes(const DevGraph &g) {
 namespace {
 
 // Shape of phys_reg_kernel for this graph (0 = none: the generic phys_kernel).
-// LDPC_PHYS_REG=0 forces phys_kernel (A/B).
+// LDPC_PHYS_REG=0 (read per launch, as LDPC_PHYS_Q_REG) forces phys_kernel
+// (tests, A/B).
 struct RegShape {
     int rpt, rdeg, cpt, cdeg;
 };
@@ -259,11 +260,9 @@ constexpr int kRegNT = 512;
 constexpr RegShape kRegShapes[] = {{1, 8, 1, 8}, {1, 8, 2, 8}, {2, 8, 3, 8}, {2, 16, 5, 8}, {3, 8, 5, 8}};
 
 int reg_shape(const DevGraph &g) {
-    static const int force = [] {
-        const char *e = getenv("LDPC_PHYS_REG");
-        return e ? atoi(e) : -1;
-    }();
-    if (force == 0 || g.nnz >= 65536 || g.n >= 65536) return -1;  // 16-bit indices
+    if (const char *e = getenv("LDPC_PHYS_REG"))
+        if (atoi(e) == 0) return -1;
+    if (g.nnz >= 65536 || g.n >= 65536) return -1;  // 16-bit indices
     const int mc = g.max_col_deg;
     const int rpt = (g.m + kRegNT - 1) / kRegNT, cpt = (g.n + kRegNT - 1) / kRegNT;
     int best = -1;

@@ -273,11 +273,12 @@ __global__ __launch_bounds__(256) void phys_vn_tile_kernel(DevGraph g, DevState 
                     p0[q] = j < j1 ? csc_ptr[j] : 0;
                     cd[q] = j < j1 ? csc_ptr[j + 1] - p0[q] : 0;
                 }
-                // lane-masked: converged / finished frames move no data
+                // lane-masked: converged / finished frames move no data.  Lambda
+                // for every column below n: one without edges keeps L = Lambda
 #pragma unroll
                 for (int q = 0; q < CB; ++q) {
                     La[q] = 0.0f;
-                    if (upd && cd[q] > 0) La[q] = Lamt[(j0 + b * CB + q) * kTile];
+                    if (upd && j0 + b * CB + q < j1) La[q] = Lamt[(j0 + b * CB + q) * kTile];
 #pragma unroll
                     for (int i = 0; i < kCD; ++i) {
                         Ev[q][i] = 0.0f;

@@ -93,7 +93,8 @@ constexpr int kSR = 4;  // chain slots
 // by the p3dep waits; ds_add_f64 rounds to nearest even and, unlike the other
 // LDS float atomics, never flushes denormals (LLVM SIISelLowering emits it for
 // workgroup-scope fadd only on that basis; +2 %, profiles/r4za_ab).  A fresh
-// streaming frame's lanes (and iteration 0) read no E_old: M = L - 0.0 == L.
+// streaming frame's lanes read no E_old: M = L - 0.0 == L; iteration 0 of the
+// static decoder reads neither E_old nor ch: its t comes from sub_tanh_table.
 // Measured and not kept (profiles/ READMEs; git history has the code): tanh
 // groups of 2-3 slots in lockstep (spills), guarded per-slot P1/P3 forms,
 // skipping the padded slot K-1 (0.4375), sc1 E_new stores (0.436), uint16
@@ -115,7 +116,7 @@ constexpr uint32_t kSubOOB = 0xfffffff0u;
 __device__ __forceinline__ void st_sub_msg(__amdgpu_buffer_rsrc_t r, uint32_t off, double v) {
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(sub_u2, v), r, off, 0, 2 /* nt */);
 }
-// E_old loads the same way: at kSubOOB (iteration 0, a fresh frame) the
+// E_old loads the same way: at kSubOOB (a fresh frame, a masked slot) the
 // hardware returns 0 without a memory request
 __device__ __forceinline__ double ld_sub_msg(__amdgpu_buffer_rsrc_t r, uint32_t off) {
     return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 2 /* nt */));
@@ -287,25 +288,42 @@ __device__ __forceinline__ bool sub_p1(const SubCtx<Q> &c, int r, const SubChunk
     constexpr int K = SubCfg<Q>::K;
     bool tiny = false;
     const int sv = sub_stage_issue(c, r + 1);  // row r+1's indices, committed below
-    if (rc.cnt > 0) {
+    if (rc.cnt > 0 && c.first) {
+        // Iteration 0 of the static decoder (uniform): E_old = 0 and M = ch, so
+        // t depends on (column, frame) only and sub_tanh_table has left it in
+        // L[col] -- one gather per slot where the other passes gather the
+        // posterior, no E_old request, no tanh.  A frame-less lane's L holds
+        // no table (it may hold a finished frame's outputs): its slots are 1.0.
+        const int njt = c.live ? sub_nj(c, rc) : 0;
+        const uint16_t *lc = sub_lcols(c, r, rc);
+        int col[K];
+#pragma unroll
+        for (int i = 0; i < K; ++i) col[i] = lc[i];
+#pragma unroll
+        for (int i = 0; i < K; ++i) t[i] = ld_l2((const double *)(c.Lu + sub_off(c, col[i])));
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            tiny |= i < njt && !(fabs(t[i]) > kTiny);
+            t[i] = i < njt ? t[i] : 1.0;
+        }
+    } else if (rc.cnt > 0) {
         const int nj = sub_nj(c, rc);
         const int njt = c.live ? nj : 0;  // the |t| <= 1e-10 vote: frame-less lanes abstain
         const uint16_t *lc = sub_lcols(c, r, rc);
         const uint32_t eoff = sub_eoff(c, rc);
-        // iteration 0 / a fresh streaming frame: M = L
-        const bool noE = c.first || c.fresh;
+        // a fresh streaming frame: M = L
+        const bool noE = c.fresh;
         int col[K];
         double eo[K];
 #pragma unroll
         for (int i = 0; i < K; ++i) {
-            // iteration 0 and a fresh frame's lanes read no E_old (on a
-            // streaming pass most slots hold fresh frames)
+            // a fresh frame's lanes read no E_old (on a streaming pass most
+            // slots hold fresh frames)
             eo[i] = ld_sub_msg(c.rE, noE ? kSubOOB : eoff + (uint32_t)i * (kTile * sizeof(double)));
             col[i] = lc[i];
         }
-        const char *Lsrc = c.first ? c.Cu : c.Lu;  // iteration 0: M = ch (:85-90); uniform
 #pragma unroll
-        for (int i = 0; i < K; ++i) t[i] = ld_l2((const double *)(Lsrc + sub_off(c, col[i])));
+        for (int i = 0; i < K; ++i) t[i] = ld_l2((const double *)(c.Lu + sub_off(c, col[i])));
 #pragma unroll
         for (int i = 0; i < K; ++i) {
             const double M = noE ? t[i] : t[i] - eo[i];  // :85-90 / :260-268
@@ -322,6 +340,26 @@ __device__ __forceinline__ bool sub_p1(const SubCtx<Q> &c, int r, const SubChunk
     }
     sub_stage_commit(c, r + 1, sv);
     return __ballot(tiny) != 0ull;
+}
+
+// Iteration 0's tanh, once per column and frame instead of once per edge (575
+// edges per column of wimax_2304_0.5): T[col][f] = np_tanh(clamp(ch[col][f]/2))
+// by sub_p1's own expression, so the bits are the ones its per-edge evaluation
+// gives.  T lives in the tile's L, which the static decoder does not read in
+// iteration 0 (the column sweep compares with ch) and overwrites column by
+// column for every live frame: the A columns in the column sweep after the row
+// loop, the identity column k + r in P3(r) -- read before that only by P1(r) of
+// the same wavefront, the one that holds the row's last edge.  Frame-less lanes
+// leave L alone.  The whole workgroup, (wavefront, lane group) pair `me` of
+// `nthr` taking every nthr-th column; the caller makes the stores visible.
+template <int Q>
+__device__ __forceinline__ void sub_tanh_table(const SubCtx<Q> &c, int n, int me, int nthr) {
+    for (int col = me; col < n; col += nthr) {
+        const double d = *sub_c(c, col) * 0.5;
+        double th[1] = {dfrom(dbits(fmin(fabs(d), 17.5)) | (dbits(d) & 0x8000000000000000ull))};
+        np_tanh_n<1, LdsTanh, true>(th, c.ttab);
+        if (c.live) *sub_l(c, col) = th[0];
+    }
 }
 
 // Lane-group hand-over for Q = 4 (lane = j*16 + f: group j is DPP row j) with
@@ -548,9 +586,12 @@ __device__ __forceinline__ void sub_p3_body(SubCtx<Q> &c, int r, double (&t)[Sub
         // each own E_new store replaces is loaded again through the buffer
         // resource (masked slots at kSubOOB request nothing) and compared with
         // E_new bit for bit; a difference sets the frame's flag.  The loads
-        // are compared, so they have returned, before the stores below issue.
+        // are compared, so they have returned, before the stores issue.
         // Here and not ahead of the chain wait: E_old held from there costs 20
         // registers of every pass's row loop, this block none outside itself.
+        // Only the slots that differ are stored (the others at kSubOOB, which
+        // the hardware drops): memory holds E_new either way, and at a fixed
+        // point no slot differs -- the pass writes no message at all.
         const uint32_t eoff = sub_eoff(c, rc);
         const int njv = c.live ? nj : 0;
         double eold[K];
@@ -559,10 +600,13 @@ __device__ __forceinline__ void sub_p3_body(SubCtx<Q> &c, int r, double (&t)[Sub
             eold[i] = ld_sub_msg(c.rE, i < njv ? eoff + (uint32_t)i * (kTile * sizeof(double)) : kSubOOB);
         bool d = false;
 #pragma unroll
-        for (int i = 0; i < K; ++i) d |= i < njv && dbits(eold[i]) != dbits(t[i]);
+        for (int i = 0; i < K; ++i) {
+            const bool di = i < njv && dbits(eold[i]) != dbits(t[i]);
+            d |= di;
+            st_sub_msg(c.rE, di ? eoff + (uint32_t)i * (kTile * sizeof(double)) : kSubOOB, t[i]);
+        }
         if (d) atomicOr((uint32_t *)c.mdiff + (threadIdx.x & (F - 1)), 1u);
-    }
-    {
+    } else {
         const uint32_t eoff = sub_eoff(c, rc);
 #pragma unroll
         for (int i = 0; i < K; ++i)  // nj <= CS
@@ -655,7 +699,8 @@ __device__ __forceinline__ void sub_body(SubCtx<Q> &c, int r, int m, double (&tc
 //            previous one (ch on iteration 0) bit for bit: pdiffl[f];
 //   verify   a pass at iteration >= 1, when some running frame's posteriors
 //            repeated in the pass before, compares every own E_new with the
-//            E_old it replaces (c.verify, sub_p3_body): mdiffl[f].  The
+//            E_old it replaces (c.verify, sub_p3_body): mdiffl[f], and stores
+//            only the ones that differ (at a fixed point: none).  The
 //            identity columns need no check: for iteration >= 1
 //            L = ch + (0 + E) of the row's last edge repeats if E does;
 //   exit     after a verifying pass, a running frame with no message and no
@@ -759,6 +804,12 @@ __global__ __launch_bounds__(64 * kSW, 1) void tile_sub_kernel(DevGraph g, DevSt
     // posteriors repeated, 4: a frame stopped at a fixed point); the next
     // verifying pass is allowed at iteration vnext, after a gap of vgap passes
     int ctl = 1, vnext = 1, vgap = 1;
+    if (max_iter > 0) {  // iteration 0's tanh table, in L (sub_tanh_table); the other wavefronts gather it with ld_l2
+        c.live = livel[f] != 0;
+        sub_tanh_table<Q>(c, g.n, me, nthr);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        __syncthreads();
+    }
     for (int it = 0; it < max_iter; ++it) {
         c.first = it == 0;
         c.live = livel[f] != 0;

@@ -53,6 +53,8 @@ extern "C" {
                                    column k + (131 F + 7) mod m and information column (37 F + 3) mod k,
                                    so their rows take spa_decoder.py:159-164's |t| <= 1e-10 branch (an
                                    identity column's M = (0 + E) - E is 0 on every iteration) */
+#define LDPC_F_LAYERED_TILE 0x40u /* physical mode, LDPC_SCHED_LAYERED: the HBM tile kernels even if
+                                     the state fits LDS (tests, A/B); LDPC_EINVAL with LDPC_SCHED_FLOODING */
 
 typedef struct ldpc_hstd ldpc_hstd;       /* standard-form parity-check matrix  */
 typedef struct ldpc_graph ldpc_graph;     /* H_std uploaded to one GPU          */
@@ -116,8 +118,9 @@ const char *ldpc_tile_kernel_name(const ldpc_graph *g);
 const char *ldpc_phys_kernel_name(const ldpc_graph *g, uint32_t flags);
 /* The same for a check-node rule and schedule (LDPC_CN_*, LDPC_SCHED_*, below):
  * the flooding names above whatever the rule (the rule is a template parameter
- * of those kernels), "phys_layered_kernel" for the layered schedule, "" for a
- * combination ldpc_phys_decode_ex rejects. */
+ * of those kernels); for the layered schedule "phys_layered_kernel" (state in
+ * LDS) or "phys_layer_tile_kernel" (state in HBM: LDPC_F_LAYERED_TILE, or a
+ * graph too large for LDS); "" for a combination ldpc_phys_decode_ex rejects. */
 const char *ldpc_phys_kernel_name_ex(const ldpc_graph *g, uint32_t flags, int32_t cn_rule, int32_t schedule);
 int ldpc_graph_info(const ldpc_graph *g, int32_t *m, int32_t *n, int64_t *nnz,
                     int32_t *max_row_deg, int32_t *max_col_deg);
@@ -245,11 +248,21 @@ int ldpc_phys_mc_run(ldpc_decoder *d_std, const ldpc_graph *g_phys, uint64_t see
  *                        iteration see the earlier ones' posteriors.
  * Both stop after the first full iteration whose b = (L < 0) has H b = 0.
  * Supported: SPA flooding (= ldpc_phys_decode, the default); NMS / OMS flooding
- * on the LDS and the HBM path (bit-identical); NMS / OMS layered on the LDS
- * path (E and L in LDS: ldpc_phys_lds_bytes minus 4 n bytes <= ~159 KB).
- * SPA layered is LDPC_EINVAL; layered with LDPC_F_PHYS_HBM or on a graph too
- * large for LDS is LDPC_ERANGE.  The min-sum results equal a CPU restatement
- * of these rules bit for bit (tests/minsum_ref.py). */
+ * on the LDS and the HBM path (bit-identical); NMS / OMS layered with E and L
+ * in LDS when they fit (ldpc_phys_lds_bytes minus 4 n bytes <= ~159 KB:
+ * phys_layered_kernel), else -- or with LDPC_F_LAYERED_TILE -- on the HBM
+ * tiles (phys_layer_tile_kernel, csrc/phys_tile.hip: one launch per layer and
+ * iteration, then a syndrome sweep and the exit on the device; the DVB-S2
+ * profile takes this path with no flag).  Both layered paths do the same
+ * operations in the same order: bit-identical.  Monte-Carlo runs on the tile
+ * path compact as ldpc_phys_mc_run does; ldpc_phys_decode_ex there works in
+ * chunks of 1024 frames and synchronises before it returns, as the flooding
+ * HBM path.
+ * SPA layered is LDPC_EINVAL, and so is LDPC_F_LAYERED_TILE with
+ * LDPC_SCHED_FLOODING; layered with LDPC_F_PHYS_HBM (the flooding tile
+ * kernels' flag), with or without LDPC_F_LAYERED_TILE, is LDPC_ERANGE.  The
+ * min-sum results equal a CPU restatement of these rules bit for bit
+ * (tests/minsum_ref.py). */
 #define LDPC_CN_SPA 0
 #define LDPC_CN_NMS 1
 #define LDPC_CN_OMS 2
@@ -304,7 +317,7 @@ int ldpc_layers_build(int32_t m, int32_t n, const int32_t *row_ptr, const int32_
  * [0, 0, 0, (36 + 8) >> 4 = 2], parity 1: R = [0, 0, 0, -2].  With llr_scale 4,
  * llr 0.625 gives Lam -2 and llr 0.875 gives Lam -4 (both ties round to even).
  * A frame's state (int8 E, int16 L, int8 Lam) lives in LDS
- * (ldpc_phys_q_lds_bytes; n < 65535).  With LDPC_F_PHYS_HBM, or on a graph
+ * (ldpc_phys_q_lds_bytes; n < 65535).  With LDPC_F_PHYS_HBM or LDPC_F_LAYERED_TILE, or on a graph
  * whose quantized state does not fit, the calls return LDPC_ERANGE;
  * LDPC_CN_SPA, a row of fewer than 2 edges, or a parameter out of range is
  * LDPC_EINVAL.  Every check runs before any device work.  The results equal a

@@ -59,6 +59,7 @@ struct ldpc_graph {
     mutable std::string layers_err;
     mutable int *d_layers = nullptr;  // layer_ptr [n_layers + 1], then layer_rows [m]
     mutable int n_layers = 0, max_layer = 0;
+    mutable std::vector<int> h_layer_ptr;  // layer_ptr on the host (launch sizes of the tile path)
     // padded message layout of the fixed-point decoder (phys_quant.hip): built and
     // uploaded on the graph's first quantized decode (graph_quant_tab), likewise
     mutable std::once_flag qtab_once;
@@ -694,10 +695,10 @@ const char *ldpc_phys_kernel_name(const ldpc_graph *g, uint32_t flags) {
 
 const char *ldpc_phys_kernel_name_ex(const ldpc_graph *g, uint32_t flags, int32_t cn_rule, int32_t schedule) {
     if (!g || cn_rule < LDPC_CN_SPA || cn_rule > LDPC_CN_OMS) return "";
-    if (schedule == LDPC_SCHED_FLOODING) return ldpc_phys_kernel_name(g, flags);
-    if (schedule != LDPC_SCHED_LAYERED || cn_rule == LDPC_CN_SPA || (flags & LDPC_F_PHYS_HBM) ||
-        ldpc::phys_layered_lds_bytes(g->dg) > kLdsLimit)
-        return "";
+    if (schedule == LDPC_SCHED_FLOODING) return (flags & LDPC_F_LAYERED_TILE) ? "" : ldpc_phys_kernel_name(g, flags);
+    if (schedule != LDPC_SCHED_LAYERED || cn_rule == LDPC_CN_SPA || (flags & LDPC_F_PHYS_HBM)) return "";
+    if ((flags & LDPC_F_LAYERED_TILE) || ldpc::phys_layered_lds_bytes(g->dg) > kLdsLimit)
+        return "phys_layer_tile_kernel";
     return "phys_layered_kernel";
 }
 
@@ -1333,6 +1334,7 @@ int graph_layers(const ldpc_graph *g, PhysRule *rule) {
             return;
         }
         g->d_layers = d;
+        g->h_layer_ptr.assign(tab.begin(), tab.begin() + nl + 1);
         g->n_layers = nl;
         g->max_layer = biggest;
     });
@@ -1341,7 +1343,13 @@ int graph_layers(const ldpc_graph *g, PhysRule *rule) {
     rule->layer_rows = g->d_layers + g->n_layers + 1;
     rule->n_layers = g->n_layers;
     rule->max_layer = g->max_layer;
+    rule->h_layer_ptr = g->h_layer_ptr.data();
     return LDPC_OK;
+}
+
+// Whether the layered schedule on graph P runs the HBM tile kernels.
+bool layered_use_tile(const DevGraph &P, uint32_t flags) {
+    return (flags & LDPC_F_LAYERED_TILE) || ldpc::phys_layered_lds_bytes(P) > kLdsLimit;
 }
 
 // Validate (cn_rule, schedule, param) for graph g and fill the kernels' rule;
@@ -1362,13 +1370,17 @@ int phys_rule(const char *fn, const ldpc_graph *g, uint32_t flags, int32_t cn_ru
     if (cn_rule != LDPC_CN_SPA && g->min_row_deg < 2)
         return ldpc_fail(LDPC_EINVAL, "%s: min-sum needs every check row to have at least 2 edges (a row has %d)",
                          fn, g->min_row_deg);
+    if ((flags & LDPC_F_LAYERED_TILE) && schedule != LDPC_SCHED_LAYERED)
+        return ldpc_fail(LDPC_EINVAL, "%s: LDPC_F_LAYERED_TILE needs LDPC_SCHED_LAYERED", fn);
     *rule = PhysRule{};
     rule->cn = cn_rule;
     rule->param = cn_rule == LDPC_CN_SPA ? 0.0f : param;
     if (schedule == LDPC_SCHED_LAYERED) {
-        if ((flags & LDPC_F_PHYS_HBM) || ldpc::phys_layered_lds_bytes(g->dg) > kLdsLimit)
-            return ldpc_fail(LDPC_ERANGE, "%s: the layered schedule runs only with a frame's state in LDS "
-                                          "(not with LDPC_F_PHYS_HBM, nor on a graph too large for LDS)", fn);
+        if (flags & LDPC_F_PHYS_HBM)
+            return ldpc_fail(LDPC_ERANGE, "%s: LDPC_F_PHYS_HBM selects the flooding tile kernels; the layered "
+                                          "schedule's HBM path is LDPC_F_LAYERED_TILE", fn);
+        // the HBM tile kernels on request, and for a graph too large for LDS
+        rule->layered_tile = layered_use_tile(g->dg, flags);
         return graph_layers(g, rule);
     }
     return LDPC_OK;
@@ -1425,6 +1437,65 @@ int phys_decode_lds(const ldpc_graph *g, int32_t batch, const double *llr, int32
     return rc;
 }
 
+// the running counts the tile kernels keep for the host: [2 max_iter] tiles, then frames
+int ensure_pactive(ldpc_decoder *d, int max_iter) {
+    if (d->pactive_cap >= 2 * max_iter) return LDPC_OK;
+    (void)hipFree(d->pactive);
+    d->pactive = nullptr;
+    d->pactive_cap = 0;
+    if (int rc = dev_alloc(&d->pactive, 2 * (size_t)max_iter)) return rc;
+    d->pactive_cap = 2 * max_iter;
+    return LDPC_OK;
+}
+
+// LDPC_PHYS_COMPACT=0: no compaction (A/B, diagnosis; the counters are the same)
+bool phys_compact_enabled() {
+    const char *e = getenv("LDPC_PHYS_COMPACT");
+    return !e || atoi(e) != 0;
+}
+
+// The layered schedule on the tiles (phys_tile.hip): per iteration one launch
+// per layer, in order on the stream, then the syndrome of b = (L < 0) and the
+// exits -- on the device every iteration, so the results never depend on the
+// polls.  The host polls and compacts as phys_tile_decode does; the exit of
+// iteration max_iter - 1 stops the frames still running (no final sweep).
+int phys_tile_decode_layered(ldpc_decoder *d, const DevGraph &P, int max_iter, bool from_ch, hipStream_t s,
+                             unsigned long long *ctr, const PhysRule &rule) {
+    if (int rc = ensure_pactive(d, max_iter)) return rc;
+    DevState st = d->st;  // st.ntiles shrinks with each compaction
+    const PhysTile pt = phys_tile(d);
+    const int cap = d->cap_tiles * kTile;
+    const bool compact = phys_compact_enabled();
+    HIP_TRY(hipMemsetAsync(d->pactive, 0, sizeof(int) * 2 * max_iter, s));
+    HIP_TRY(ldpc::launch_phys_tile_init(P, st, pt, from_ch, s));
+    for (int it = 0; it < max_iter; ++it) {
+        HIP_TRY(timed(d, LDPC_K_PHYS_CN, s, [&] {
+            for (int l = 0; l < rule.n_layers; ++l) {
+                const int lbeg = rule.h_layer_ptr[l], lrows = rule.h_layer_ptr[l + 1] - lbeg;
+                if (hipError_t e = ldpc::launch_phys_layer_tile(P, st, pt, it, lbeg, lrows, s, rule)) return e;
+            }
+            return hipSuccess;
+        }));
+        HIP_TRY(timed(d, LDPC_K_PHYS_VN, s,
+                      [&] { return ldpc::launch_phys_layer_exit(P, st, pt, it, d->pactive, max_iter, s); }));
+        if (it + 1 < max_iter && (it < 4 || (it + 1) % 4 == 0)) {
+            int running[2] = {0, 0};  // tiles, frames
+            HIP_TRY(hipMemcpyAsync(&running[0], d->pactive + it, sizeof(int), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(&running[1], d->pactive + max_iter + it, sizeof(int), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            if (running[0] == 0) break;  // every frame has stopped
+            const int nt = (running[1] + kTile - 1) / kTile;
+            if (ctr && compact && nt < st.ntiles && 4 * (int64_t)running[1] <= (int64_t)st.ntiles * kTile) {
+                if (!d->cpairs && dev_alloc(&d->cpairs, 1 + 2 * (size_t)cap)) return LDPC_ENOMEM;
+                HIP_TRY(timed(d, LDPC_K_COUNT, s, [&] { return ldpc::launch_phys_tile_count(P, st, pt, ctr, s); }));
+                HIP_TRY(ldpc::launch_phys_compact(P, st, pt, nt, cap, d->cpairs, s));
+                st.ntiles = nt;
+            }
+        }
+    }
+    return LDPC_OK;
+}
+
 // Decode the frames bound in d->st (channel LLRs in d->ch) on graph P with the
 // HBM-resident tile kernels: up to max_iter CN+VN sweeps, then a syndrome-only
 // sweep.  The host reads the running-tile and running-frame counts after
@@ -1435,21 +1506,12 @@ int phys_decode_lds(const ldpc_graph *g, int32_t batch, const double *llr, int32
 // into ctr first (phys_tile.hip).
 int phys_tile_decode(ldpc_decoder *d, const DevGraph &P, int max_iter, bool from_ch, hipStream_t s,
                      unsigned long long *ctr = nullptr, const PhysRule &rule = PhysRule{}) {
-    if (d->pactive_cap < 2 * max_iter) {
-        (void)hipFree(d->pactive);
-        d->pactive = nullptr;
-        d->pactive_cap = 0;
-        if (int rc = dev_alloc(&d->pactive, 2 * (size_t)max_iter)) return rc;
-        d->pactive_cap = 2 * max_iter;
-    }
+    if (rule.layer_ptr) return phys_tile_decode_layered(d, P, max_iter, from_ch, s, ctr, rule);
+    if (int rc = ensure_pactive(d, max_iter)) return rc;
     DevState st = d->st;  // st.ntiles shrinks with each compaction
     const PhysTile pt = phys_tile(d);
     const int cap = d->cap_tiles * kTile;
-    // LDPC_PHYS_COMPACT=0: no compaction (A/B, diagnosis; the counters are the same)
-    const bool compact = [] {
-        const char *e = getenv("LDPC_PHYS_COMPACT");
-        return !e || atoi(e) != 0;
-    }();
+    const bool compact = phys_compact_enabled();
     HIP_TRY(hipMemsetAsync(d->pactive, 0, sizeof(int) * 2 * max_iter, s));
     HIP_TRY(ldpc::launch_phys_tile_init(P, st, pt, from_ch, s));
     for (int it = 0; it < max_iter; ++it) {
@@ -1550,7 +1612,7 @@ int phys_decode_any(const char *fn, const ldpc_graph *g, int32_t batch, const do
     if (int rc = phys_rule(fn, g, flags, cn_rule, schedule, param, &rule)) return rc;
     if (batch == 0) return LDPC_OK;
     hipStream_t s = (hipStream_t)stream;
-    if (rule.layer_ptr || phys_use_lds(g->dg, flags))
+    if (rule.layer_ptr ? !rule.layered_tile : phys_use_lds(g->dg, flags))
         return phys_decode_lds(g, batch, llr, max_iter, flags, z_out, conv_out, status_out, iters_out, post_out, s,
                                rule);
     return phys_decode_tile(g, batch, llr, max_iter, flags, z_out, conv_out, status_out, iters_out, post_out, s, rule);
@@ -1576,7 +1638,7 @@ int phys_mc_any(const char *fn, ldpc_decoder *d, const ldpc_graph *gp, uint64_t 
     PhysRule rule;
     if (int rc = phys_rule(fn, gp, flags, cn_rule, schedule, param, &rule)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const bool lds = rule.layer_ptr || phys_use_lds(P, flags);
+    const bool lds = rule.layer_ptr ? !rule.layered_tile : phys_use_lds(P, flags);
     if (!lds)
         if (int rc = ensure_phys_tile(d, P)) return rc;
     if (int rc = ensure_pbits(d, G)) return rc;
@@ -1693,9 +1755,9 @@ int quant_check(const char *fn, const ldpc_graph *g, uint32_t flags, int32_t cn_
     if (g->min_row_deg < 2)
         return ldpc_fail(LDPC_EINVAL, "%s: min-sum needs every check row to have at least 2 edges (a row has %d)",
                          fn, g->min_row_deg);
-    if (flags & LDPC_F_PHYS_HBM)
+    if (flags & (LDPC_F_PHYS_HBM | LDPC_F_LAYERED_TILE))
         return ldpc_fail(LDPC_ERANGE, "%s: the fixed-point decoder runs only with a frame's state in LDS "
-                                      "(not with LDPC_F_PHYS_HBM)", fn);
+                                      "(not with LDPC_F_PHYS_HBM or LDPC_F_LAYERED_TILE)", fn);
     if (!quant_fits(g, schedule == LDPC_SCHED_LAYERED))
         return ldpc_fail(LDPC_ERANGE, "%s: the graph's quantized state (%lld bytes, n = %d) does not fit LDS", fn,
                          (long long)ldpc::phys_quant_lds_bytes(g->dg, quant_epad(g),
@@ -1787,7 +1849,8 @@ const char *ldpc_phys_kernel_name_q(const ldpc_graph *g, uint32_t flags, int32_t
                                     int32_t qbits) {
     if (!g || (cn_rule != LDPC_CN_NMS && cn_rule != LDPC_CN_OMS) ||
         (schedule != LDPC_SCHED_FLOODING && schedule != LDPC_SCHED_LAYERED) || qbits < 4 || qbits > 8 ||
-        g->min_row_deg < 2 || (flags & LDPC_F_PHYS_HBM) || !quant_fits(g, schedule == LDPC_SCHED_LAYERED))
+        g->min_row_deg < 2 || (flags & (LDPC_F_PHYS_HBM | LDPC_F_LAYERED_TILE)) ||
+        !quant_fits(g, schedule == LDPC_SCHED_LAYERED))
         return "";
     const bool layered = schedule == LDPC_SCHED_LAYERED;
     return ldpc::phys_quant_reg_shape(g->dg, quant_epad(g), layered) >= 0 ? "phys_quant_reg_kernel" : "phys_quant_kernel";

@@ -28,6 +28,8 @@
 // sweep (profiles/r5s_c5).  done[]: 0 running, 1 finished (to be counted),
 // 2 counted, moved away, or no frame.  Each (tile, row block) and (tile, column
 // block) is placed XCD-aware like cn_kernel.
+// The layered min-sum schedule runs on the same tiles (phys_layer_tile: one
+// launch per layer, then a syndrome sweep and the exit; further down).
 // Frames come from frame_kernels.hip (directly as fp32 Lambda/L for IRA
 // codes, else as fp64 ch converted by phys_tile_init).
 #include <hip/hip_runtime.h>
@@ -495,6 +497,167 @@ __global__ void phys_compact_flags_kernel(DevState st, PhysTile pt, int cap, con
     st.done[src] = 2;  // moved: nothing to count here
 }
 
+// ------------------------------------------- layered min-sum on the tiles
+// The layered schedule (phys_layered.hip's arithmetic, operation for
+// operation: bit-identical) with E32 / L32 in HBM.  One launch per layer and
+// iteration; stream order is the ordering between layers.  A wavefront takes
+// kRowsPerWave rows of the layer, layer_rows[lbeg + ...]: rows of one layer
+// share no column, so no two wavefronts of a launch touch the same L or E
+// element.  Per row of degree <= kDeg every gather of L[c_e] and every E_e
+// load is issued first, Q = L[c_e] - E_e stays in registers with the sign
+// word and the two smallest |Q|, then E_e = R_e and L[c_e] = Q_e + R_e are
+// stored: 16 B/edge.  Longer rows take two sweeps, Q recomputed in the second
+// from the L and E the first one read (a row's columns are distinct).
+// Iteration 0 does not read E (Q = L), and every edge of a running frame is
+// written once per iteration: E needs no memset, and a compaction move (after
+// a poll, so after a whole iteration) copies written messages only.  Only the
+// lanes of running frames load or store: a stopped frame's L is its posterior.
+template <int kDeg, int CN>
+__global__ __launch_bounds__(256) void phys_layer_tile_kernel(DevGraph g, DevState st, PhysTile pt, int it, int lbeg,
+                                                              int lrows, int per_tile, int items,
+                                                              const int *__restrict__ row_ptr,
+                                                              const int *__restrict__ col_idx,
+                                                              const int *__restrict__ layer_rows, float param) {
+    const int lane = threadIdx.x & 63;
+    const int wave = uniform(threadIdx.x >> 6);
+    const bool first = it == 0;
+    for (int item = blockIdx.x; item < items; item += gridDim.x) {
+        int tile, part;
+        xcd_item(item, per_tile, tile, part);
+        if (tile >= st.ntiles || !st.tile_active[tile]) continue;
+        const int f = tile * kTile + lane;
+        const bool live = st.done[f] == 0;
+        if (__ballot(live) == 0ull) continue;
+        float *Lt = pt.L + (size_t)tile * g.n * kTile + lane;
+        float *Et = pt.E + (size_t)tile * g.nnz * kTile + lane;
+        const int i0 = (part * 4 + wave) * kRowsPerWave;
+        for (int rr = 0; rr < kRowsPerWave; ++rr) {
+            if (i0 + rr >= lrows) break;
+            const int r = uniform(layer_rows[lbeg + i0 + rr]);
+            const int beg = row_ptr[r], deg = row_ptr[r + 1] - beg;
+            if (deg <= kDeg) {
+                float Q[kDeg], Eo[kDeg];
+#pragma unroll
+                for (int i = 0; i < kDeg; ++i) {
+                    Q[i] = 0.0f;
+                    Eo[i] = 0.0f;
+                    if (i < deg && live) {
+                        Q[i] = Lt[col_idx[beg + i] * kTile];
+                        if (!first) Eo[i] = ld_e32(&Et[(beg + i) * kTile]);
+                    }
+                }
+                MinPair mp;
+                uint32_t sg = 0u;
+#pragma unroll
+                for (int i = 0; i < kDeg; ++i) {
+                    if (i < deg) {
+                        if (!first) Q[i] = Q[i] - Eo[i];
+                        mp.add(fabsf(Q[i]), i);
+                        sg |= (Q[i] < 0.0f ? 1u : 0u) << i;
+                    }
+                }
+                if (live) {
+                    const uint32_t neg = __popc(sg) & 1u;
+                    const float m1 = ms_scale<CN>(mp.min1, param), m2 = ms_scale<CN>(mp.min2, param);
+#pragma unroll
+                    for (int i = 0; i < kDeg; ++i) {
+                        if (i < deg) {
+                            const float mag = i == mp.arg ? m2 : m1;
+                            const float R = ((neg ^ (sg >> i)) & 1u) ? -mag : mag;
+                            st_e32(&Et[(beg + i) * kTile], R);
+                            Lt[col_idx[beg + i] * kTile] = Q[i] + R;
+                        }
+                    }
+                }
+            } else if (live) {
+                const int end = beg + deg;
+                MinPair mp;
+                uint32_t neg = 0u;
+                for (int e = beg; e < end; ++e) {
+                    const float Lc = Lt[col_idx[e] * kTile];
+                    const float Qe = first ? Lc : Lc - Et[e * kTile];
+                    mp.add(fabsf(Qe), e);
+                    neg ^= (Qe < 0.0f) ? 1u : 0u;
+                }
+                for (int e = beg; e < end; ++e) {
+                    const int c = col_idx[e];
+                    const float Lc = Lt[c * kTile];
+                    const float Qe = first ? Lc : Lc - ld_e32(&Et[e * kTile]);
+                    const float mag = ms_scale<CN>(mp.other(e), param);
+                    const float R = ((neg ^ ((Qe < 0.0f) ? 1u : 0u)) != 0u) ? -mag : mag;
+                    st_e32(&Et[e * kTile], R);
+                    Lt[c * kTile] = Qe + R;
+                }
+            }
+        }
+    }
+}
+
+// After the last layer of an iteration: the row parities of b = (L < 0) of the
+// running frames, one wavefront per (tile, 4 rows) as phys_tile_syn, read
+// from L itself -> bad[frame] (one slot: phys_layer_exit consumes and clears it).
+__global__ __launch_bounds__(256) void phys_layer_syn_kernel(DevGraph g, DevState st, PhysTile pt, int per_tile,
+                                                             int items, const int *__restrict__ row_ptr,
+                                                             const int *__restrict__ col_idx) {
+    const int lane = threadIdx.x & 63;
+    const int wave = uniform(threadIdx.x >> 6);
+    for (int item = blockIdx.x; item < items; item += gridDim.x) {
+        int tile, part;
+        xcd_item(item, per_tile, tile, part);
+        if (tile >= st.ntiles || !st.tile_active[tile]) continue;
+        const int f = tile * kTile + lane;
+        const bool live = st.done[f] == 0;
+        if (__ballot(live) == 0ull) continue;
+        const float *Lt = pt.L + (size_t)tile * g.n * kTile + lane;
+        uint32_t bad = 0u;
+        const int r0 = (part * 4 + wave) * kRowsPerWave;
+        for (int rr = 0; rr < kRowsPerWave; ++rr) {
+            const int r = r0 + rr;
+            if (r >= g.m) break;
+            uint32_t hp = 0u;
+            if (live)
+                for (int e = row_ptr[r]; e < row_ptr[r + 1]; ++e) hp ^= Lt[col_idx[e] * kTile] < 0.0f ? 1u : 0u;
+            bad |= hp;
+        }
+        if (live && bad) pt.bad[f] = 1;
+    }
+}
+
+// The exit of iteration it: a running frame with no bad row stops, converged
+// at it (phys_tile_exit); after the last iteration the frames still running
+// stop unconverged (phys_tile_final).  Runs every iteration, so the results
+// never depend on when the host polls the running counts.
+__global__ __launch_bounds__(64) void phys_layer_exit_kernel(DevState st, PhysTile pt, int it, int *active_count,
+                                                             int max_iter) {
+    const int tile = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int f = tile * kTile + lane;
+    const bool active = st.tile_active[tile] != 0;
+    const bool live = active && st.done[f] == 0;
+    const bool conv_now = live && pt.bad[f] == 0;
+    pt.bad[f] = 0;  // for the next iteration's syndrome
+    const bool last = it + 1 >= max_iter;
+    if (conv_now) {
+        st.done[f] = 1;
+        st.conv[f] = it;
+        st.status[f] = 0;
+        st.iters[f] = it + 1;
+    } else if (live && last) {
+        st.done[f] = 1;
+        st.conv[f] = -1;
+        st.status[f] = 1;
+        st.iters[f] = max_iter;
+    }
+    const unsigned long long still = __ballot(live && !conv_now && !last);
+    if (lane == 0) {
+        if (active) st.tile_active[tile] = still != 0ull ? 1 : 0;
+        if (still) {
+            atomicAdd(&active_count[it], 1);
+            atomicAdd(&active_count[max_iter + it], (int)__popcll(still));
+        }
+    }
+}
+
 inline unsigned grid_for(size_t total, int block) { return (unsigned)((total + block - 1) / block); }
 inline unsigned xcd_items(int ntiles, int per_tile) { return (unsigned)(((ntiles + 7) / 8) * 8 * per_tile); }
 // 256 CUs x 16 blocks of 4 waves (a multiple of 8, see xcd_item)
@@ -577,6 +740,49 @@ hipError_t launch_phys_tile_early_exit(const DevGraph &g, const DevState &st, co
     if (hipError_t e = hipMemsetAsync(active_count + it, 0, sizeof(int), s)) return e;
     if (hipError_t e = hipMemsetAsync(active_count + max_iter + it, 0, sizeof(int), s)) return e;
     phys_tile_exit_kernel<<<st.ntiles, kTile, 0, s>>>(st, pt, it, active_count, max_iter);
+    return hipGetLastError();
+}
+
+namespace {
+
+template <int CN>
+void launch_layer_tile_rule(const DevGraph &g, const DevState &st, const PhysTile &pt, int it, int lbeg, int lrows,
+                            const PhysRule &rule, hipStream_t s) {
+    const int per_tile = (lrows + 4 * kRowsPerWave - 1) / (4 * kRowsPerWave);
+    const int items = (int)xcd_items(st.ntiles, per_tile);
+    const unsigned grid = stride_grid(items);
+    if (g.max_row_deg <= 8)
+        phys_layer_tile_kernel<8, CN><<<grid, 256, 0, s>>>(g, st, pt, it, lbeg, lrows, per_tile, items, g.row_ptr,
+                                                           g.col_idx, rule.layer_rows, rule.param);
+    else if (g.max_row_deg <= 16)
+        phys_layer_tile_kernel<16, CN><<<grid, 256, 0, s>>>(g, st, pt, it, lbeg, lrows, per_tile, items, g.row_ptr,
+                                                            g.col_idx, rule.layer_rows, rule.param);
+    else
+        phys_layer_tile_kernel<32, CN><<<grid, 256, 0, s>>>(g, st, pt, it, lbeg, lrows, per_tile, items, g.row_ptr,
+                                                            g.col_idx, rule.layer_rows, rule.param);
+}
+
+}  // namespace
+
+hipError_t launch_phys_layer_tile(const DevGraph &g, const DevState &st, const PhysTile &pt, int it, int lbeg,
+                                  int lrows, hipStream_t s, const PhysRule &rule) {
+    if (!rule.layer_rows || lbeg < 0 || lrows < 0 || lbeg + lrows > g.m) return hipErrorInvalidValue;
+    if (lrows == 0 || st.ntiles <= 0) return hipSuccess;
+    switch (rule.cn) {
+    case kCnNms: launch_layer_tile_rule<kCnNms>(g, st, pt, it, lbeg, lrows, rule, s); break;
+    case kCnOms: launch_layer_tile_rule<kCnOms>(g, st, pt, it, lbeg, lrows, rule, s); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_phys_layer_exit(const DevGraph &g, const DevState &st, const PhysTile &pt, int it,
+                                  int *active_count, int max_iter, hipStream_t s) {
+    if (st.ntiles <= 0) return hipSuccess;
+    const int per_tile = (g.m + 4 * kRowsPerWave - 1) / (4 * kRowsPerWave);
+    const int items = (int)xcd_items(st.ntiles, per_tile);
+    phys_layer_syn_kernel<<<stride_grid(items), 256, 0, s>>>(g, st, pt, per_tile, items, g.row_ptr, g.col_idx);
+    phys_layer_exit_kernel<<<st.ntiles, kTile, 0, s>>>(st, pt, it, active_count, max_iter);
     return hipGetLastError();
 }
 

@@ -207,6 +207,8 @@ struct PhysRule {
     const int *layer_rows = nullptr; // [m]
     int n_layers = 0;
     int max_layer = 0;              // rows of the largest layer
+    const int *h_layer_ptr = nullptr;  // layer_ptr on the host (the tile path sizes a layer's launch by it)
+    bool layered_tile = false;      // layered: the HBM tile kernels (phys_tile.hip), not the LDS kernel
 };
 
 // physical mode (phys_kernels.hip)
@@ -279,6 +281,16 @@ hipError_t launch_phys_tile_vn(const DevGraph &g, const DevState &st, const Phys
 // converge there skip CN(it+1); active_count[it] / [max_iter + it] recounted
 hipError_t launch_phys_tile_early_exit(const DevGraph &g, const DevState &st, const PhysTile &pt, int it,
                                        int *active_count, int max_iter, hipStream_t s);
+// Layered min-sum on the tiles: the rows layer_rows[lbeg .. lbeg + lrows) of one
+// layer (rule.cn kCnNms / kCnOms, rule.layer_rows set); launches on one stream
+// are the order of the layers.
+hipError_t launch_phys_layer_tile(const DevGraph &g, const DevState &st, const PhysTile &pt, int it, int lbeg,
+                                  int lrows, hipStream_t s, const PhysRule &rule);
+// After an iteration's last layer: syndrome of b = (L < 0), then the exits
+// (converged at it; unconverged after it = max_iter - 1) and the running counts
+// active_count[it], active_count[max_iter + it] (zeroed by the caller).
+hipError_t launch_phys_layer_exit(const DevGraph &g, const DevState &st, const PhysTile &pt, int it,
+                                  int *active_count, int max_iter, hipStream_t s);
 // Monte-Carlo compaction of the running frames into tiles < nt (the finished ones counted first)
 hipError_t launch_phys_compact(const DevGraph &g, const DevState &st, const PhysTile &pt, int nt, int cap, int *pairs,
                                hipStream_t s);

@@ -18,8 +18,8 @@ import numpy as np
 from scipy import sparse
 
 from . import _lib
-from ._lib import (LDPC_EINVAL, LDPC_ERANGE, LDPC_F_DEVICE_PTRS, LDPC_F_NLLR, LDPC_F_PHYS_HBM, LDPC_F_SPLIT,
-                   LDPC_F_STATIC, LDPC_MC_NCOUNT, LdpcError, as_i32, check)
+from ._lib import (LDPC_EINVAL, LDPC_ERANGE, LDPC_F_DEVICE_PTRS, LDPC_F_LAYERED_TILE, LDPC_F_NLLR, LDPC_F_PHYS_HBM,
+                   LDPC_F_SPLIT, LDPC_F_STATIC, LDPC_MC_NCOUNT, LdpcError, as_i32, check)
 
 
 def _csr_arrays(H):
@@ -127,6 +127,15 @@ def phys_rule_args(cn="spa", schedule="flooding", alpha=0.75, beta=0.5):
     return CN_RULES[cn], SCHEDULES[schedule], {"spa": 0.0, "nms": alpha, "oms": beta}[cn]
 
 
+def phys_flags(hbm=False, tile=False, schedule="flooding"):
+    """The physical-mode flags: hbm forces the flooding HBM tile path, tile the
+    layered schedule's (LDPC_F_LAYERED_TILE).  tile without
+    schedule="layered" raises ValueError -- before any device call."""
+    if tile and schedule != "layered":
+        raise ValueError(f"tile=True needs schedule='layered', got {schedule!r}")
+    return (LDPC_F_PHYS_HBM if hbm else 0) | (LDPC_F_LAYERED_TILE if tile else 0)
+
+
 def phys_quant_args(cn, alpha=0.75, beta=0.5, qbits=6, llr_scale=4.0):
     """(qbits, llr_scale, param_q) of the fixed-point entries (ldpc_phys_decode_q):
     qbits in 4..8, llr_scale finite and > 0, and the float alpha / beta as the
@@ -155,30 +164,33 @@ def phys_quant_args(cn, alpha=0.75, beta=0.5, qbits=6, llr_scale=4.0):
     return qbits, llr_scale, param_q
 
 
-def phys_kernel_name(graph, hbm=False, cn="spa", schedule="flooding", qbits=None, llr_scale=4.0):
+def phys_kernel_name(graph, hbm=False, cn="spa", schedule="flooding", qbits=None, llr_scale=4.0, tile=False):
     """Measurement label: the kernel phys_decode runs for these options."""
     rule, sched, _ = phys_rule_args(cn, schedule)
+    flags = phys_flags(hbm, tile, schedule)
     if qbits is not None:
         qbits, _, _ = phys_quant_args(cn, qbits=qbits, llr_scale=llr_scale)
-        return _lib.gpu().ldpc_phys_kernel_name_q(graph.handle, LDPC_F_PHYS_HBM if hbm else 0, rule, sched,
-                                                  qbits).decode()
-    return _lib.gpu().ldpc_phys_kernel_name_ex(graph.handle, LDPC_F_PHYS_HBM if hbm else 0, rule, sched).decode()
+        return _lib.gpu().ldpc_phys_kernel_name_q(graph.handle, flags, rule, sched, qbits).decode()
+    return _lib.gpu().ldpc_phys_kernel_name_ex(graph.handle, flags, rule, sched).decode()
 
 
 def phys_decode(graph, llr, max_iter, post=False, hbm=False, cn="spa", schedule="flooding", alpha=0.75, beta=0.5,
-                ex=False, qbits=None, llr_scale=4.0):
+                ex=False, qbits=None, llr_scale=4.0, tile=False):
     """Physical-mode decode of [B, n] LLRs on a sparse graph (H[:, perm]).
 
     State in LDS when a frame fits, else in HBM (hbm=True forces HBM).
     cn / schedule / alpha / beta: phys_rule_args; the defaults are the
     sum-product flooding decoder (ldpc_phys_decode), anything else goes through
     ldpc_phys_decode_ex (ex=True: the defaults too -- the library takes the
-    same path for them either way; tests).  Layered runs on the LDS path only.
+    same path for them either way; tests).  Layered runs with the state in LDS
+    when it fits, else on the HBM tiles (tile=True forces them; it needs
+    schedule="layered"); hbm=True with layered is refused.
     qbits=4..8: the fixed-point min-sum decoder (ldpc_phys_decode_q;
     phys_quant_args turns alpha / beta into its integers) on LLRs scaled by
     llr_scale; post is then the integer posterior, int16, in units of
     1 / llr_scale.  qbits=None: the fp32 decoders, llr_scale unused."""
     rule, sched, param = phys_rule_args(cn, schedule, alpha, beta)
+    flags = phys_flags(hbm, tile, schedule)
     if qbits is not None:
         qbits, llr_scale, param_q = phys_quant_args(cn, alpha, beta, qbits, llr_scale)
     llr = np.ascontiguousarray(np.atleast_2d(np.asarray(llr, dtype=np.float64)))
@@ -190,7 +202,6 @@ def phys_decode(graph, llr, max_iter, post=False, hbm=False, cn="spa", schedule=
     status = np.empty(B, np.int32)
     iters = np.empty(B, np.int32)
     Lp = np.empty((B, n), np.float32 if qbits is None else np.int16) if post else None
-    flags = LDPC_F_PHYS_HBM if hbm else 0
     if qbits is not None:
         check("ldpc_phys_decode_q", _lib.gpu().ldpc_phys_decode_q(
             graph.handle, B, _lib.ptr(llr), int(max_iter), flags, rule, sched, qbits, llr_scale, param_q,
@@ -330,21 +341,23 @@ class Decoder:
         return out
 
     def phys_mc_run(self, phys_graph, seed, sigmas, frames_per_point, frame0, max_iter, hbm=False, cn="spa",
-                    schedule="flooding", alpha=0.75, beta=0.5, qbits=None, llr_scale=4.0):
+                    schedule="flooding", alpha=0.75, beta=0.5, qbits=None, llr_scale=4.0, tile=False):
         """Physical mode (§8 f4): same on-device frames, decoded on the sparse graph.
 
         This decoder's graph is the code's H_std (frame source) or, for an IRA
-        code, phys_graph itself.  hbm=True forces the HBM-resident tile path.
+        code, phys_graph itself.  hbm=True forces the HBM-resident tile path,
+        tile=True the layered schedule's (it needs schedule="layered").
         cn / schedule / alpha / beta as phys_decode (the defaults are
         ldpc_phys_mc_run, anything else ldpc_phys_mc_run_ex); qbits /
         llr_scale as phys_decode (ldpc_phys_mc_run_q)."""
         rule, sched, param = phys_rule_args(cn, schedule, alpha, beta)
+        flags = phys_flags(hbm, tile, schedule)
         if qbits is not None:
             qbits, llr_scale, param_q = phys_quant_args(cn, alpha, beta, qbits, llr_scale)
         sig = np.ascontiguousarray(np.asarray(sigmas, dtype=np.float64))
         out = np.zeros((len(sig), LDPC_MC_NCOUNT), np.int64)
         head = (self._h, phys_graph.handle, int(seed), len(sig), sig.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                int(frames_per_point), int(frame0), int(max_iter), LDPC_F_PHYS_HBM if hbm else 0)
+                int(frames_per_point), int(frame0), int(max_iter), flags)
         tail = (out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), None)
         if qbits is not None:
             check("ldpc_phys_mc_run_q", _lib.gpu().ldpc_phys_mc_run_q(*head, rule, sched, qbits, llr_scale, param_q,

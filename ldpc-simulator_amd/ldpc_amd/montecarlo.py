@@ -91,6 +91,19 @@ def run_sweep(decoder, snrs, blocks, max_iter, seed=20260213, nllr=False, speed=
     return local
 
 
+# Codes built in code, not loaded: IRA graphs H = [H_info | staircase] (ldpc_amd.ira),
+# physical mode only -- the graph is its own frame source (parities by accumulation),
+# and its H_std = [A | I] would be dense.
+IRA_CODES = {"dvbs2_profile_64800_0.5": "dvbs2_profile_matrix", "ira_1440_0.5": "small_ira_matrix"}
+
+
+def check_ira_mode(matrix, mode):
+    """ValueError for an IRA code name outside physical mode."""
+    if isinstance(matrix, str) and matrix in IRA_CODES and mode != "physical":
+        raise ValueError(f"{matrix} is an IRA code decoded on its sparse graph: it needs mode='physical' "
+                         "(its H_std = [A | I] is dense; parity mode has no decoder for it)")
+
+
 DECODER_TYPES = {"spa": "sumproduct", "nms": "minsum-normalized", "oms": "minsum-offset"}
 
 
@@ -103,7 +116,7 @@ def decoder_type(cn_rule="spa", schedule="flooding", qbits=None):
 
 def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65536, device=0,
              rank=0, world=1, allreduce=None, matrix_path="", mode="parity", cn_rule="spa", schedule="flooding",
-             alpha=0.75, beta=0.5, qbits=None, llr_scale=4.0):
+             alpha=0.75, beta=0.5, qbits=None, llr_scale=4.0, layered_tile=False):
     """Full sweep on this process's GPU -> SimulationResult (reference schema).
 
     mode "parity" is the reference's decoder on H_std; "physical" decodes the
@@ -111,9 +124,13 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
     check rule cn_rule ("spa", "nms", "oms"; alpha / beta) and the schedule
     ("flooding", "layered") -- those options need mode="physical".  qbits
     (4..8) selects the fixed-point min-sum decoder on LLRs scaled by llr_scale
-    (device.phys_quant_args); it needs mode="physical" and a min-sum rule."""
+    (device.phys_quant_args); it needs mode="physical" and a min-sum rule.
+    layered_tile runs the layered schedule on the HBM tile kernels even where
+    the state fits LDS (it needs schedule="layered"; a code too large for LDS
+    takes them anyway).  matrix may name an IRA code (IRA_CODES): physical
+    mode only, the graph itself is the frame source."""
     from .code import EncoderDecoderData, load_committed_code
-    from .device import Decoder, Graph, phys_quant_args, phys_rule_args
+    from .device import Decoder, Graph, phys_flags, phys_quant_args, phys_rule_args
     if mode not in ("parity", "physical"):
         raise ValueError(f"mode must be 'parity' or 'physical', got {mode!r}")
     phys_rule_args(cn_rule, schedule, alpha, beta)  # ValueError before any device call
@@ -123,7 +140,14 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
         if mode != "physical":
             raise ValueError("qbits needs mode='physical'")
         phys_quant_args(cn_rule, alpha, beta, qbits, llr_scale)
+    phys_flags(tile=layered_tile, schedule=schedule)
+    check_ira_mode(matrix, mode)
     t0 = time.time()
+    if isinstance(matrix, str) and matrix in IRA_CODES:
+        from . import ira
+        return _simulate_graph(getattr(ira, IRA_CODES[matrix])(), matrix, t0, snrs, blocks, max_iter, seed, chunk,
+                               device, rank, world, allreduce, matrix_path, cn_rule, schedule, alpha, beta, qbits,
+                               llr_scale, layered_tile)
     if isinstance(matrix, EncoderDecoderData):
         edd = matrix
     elif isinstance(matrix, str) and os.path.exists(matrix):
@@ -138,7 +162,7 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
 
         def counter_fn(sigmas, cnt, frame0):
             return dec.phys_mc_run(gp, seed, sigmas, cnt, frame0, max_iter, cn=cn_rule, schedule=schedule,
-                                   alpha=alpha, beta=beta, qbits=qbits, llr_scale=llr_scale)
+                                   alpha=alpha, beta=beta, qbits=qbits, llr_scale=llr_scale, tile=layered_tile)
     ctr = run_sweep(dec, snrs, blocks, max_iter, seed=seed, nllr=nllr, rank=rank, world=world,
                     allreduce=allreduce, counter_fn=counter_fn)
     pts = point_results(ctr, edd._k, snrs, matrix_path=matrix_path or str(matrix), max_iter=max_iter)
@@ -151,9 +175,35 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
     return SimulationResult(config=cfg, snr_points=pts, wall_clock_seconds=time.time() - t0), ctr
 
 
+def _simulate_graph(H, name, t0, snrs, blocks, max_iter, seed, chunk, device, rank, world, allreduce, matrix_path,
+                    cn_rule, schedule, alpha, beta, qbits, llr_scale, layered_tile):
+    """simulate() in physical mode on an IRA graph H: one graph, the decoder's
+    frame source and the graph it decodes on (as bench.py's config 5)."""
+    from .device import Decoder, Graph
+    m, n = H.shape
+    k = n - m
+    g = Graph(H, device=device)
+    dec = Decoder(g, Decoder.fit_slots(g, min(max(1, shard(int(blocks), rank, world)[1]), chunk)))
+
+    def counter_fn(sigmas, cnt, frame0):
+        return dec.phys_mc_run(g, seed, sigmas, cnt, frame0, max_iter, cn=cn_rule, schedule=schedule, alpha=alpha,
+                               beta=beta, qbits=qbits, llr_scale=llr_scale, tile=layered_tile)
+    ctr = run_sweep(dec, snrs, blocks, max_iter, seed=seed, rank=rank, world=world, allreduce=allreduce,
+                    counter_fn=counter_fn)
+    pts = point_results(ctr, k, snrs, matrix_path=matrix_path or name, max_iter=max_iter)
+    cfg = SimulationConfig(
+        matrix_path=matrix_path or name, n=n, m=m, k=k, rate=k / n, blocks=int(blocks),
+        max_iterations=int(max_iter), encoding_method="standard", interleaver_type="none",
+        decoder_type=decoder_type(cn_rule, schedule, qbits), channel_mode=1, modulation=1, speed=1.0,
+        snr_range=(snrs[0], snrs[-1], (snrs[1] - snrs[0]) if len(snrs) > 1 else 0.0), threads=world,
+        timestamp=datetime.now().isoformat())
+    return SimulationResult(config=cfg, snr_points=pts, wall_clock_seconds=time.time() - t0), ctr
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description="GPU BER/FER sweep (main.py semantics, AWGN mode 1, BPSK)")
-    ap.add_argument("--matrix", required=True, help="ALIST path or a committed code name")
+    ap.add_argument("--matrix", required=True,
+                    help="ALIST path, a committed code name, or (physical mode) " + " / ".join(sorted(IRA_CODES)))
     ap.add_argument("-b", "--blocks", type=int, default=1000)
     ap.add_argument("-i", "--iterations", type=int, default=5)
     ap.add_argument("--initial-snr", type=float, default=0.0)
@@ -169,6 +219,8 @@ def build_parser():
                     help="physical mode: sum-product, normalized or offset min-sum")
     ap.add_argument("--schedule", choices=("flooding", "layered"), default="flooding",
                     help="physical mode: layered needs a min-sum rule")
+    ap.add_argument("--layered-tile", action="store_true",
+                    help="physical mode, --schedule layered: the HBM tile kernels even where the state fits LDS")
     ap.add_argument("--alpha", type=float, default=None, help="normalized min-sum factor in (0, 1] (default 0.75)")
     ap.add_argument("--beta", type=float, default=None, help="offset min-sum offset >= 0 (default 0.5)")
     ap.add_argument("--qbits", type=int, default=None,
@@ -181,7 +233,7 @@ def build_parser():
 def parse_args(argv=None):
     """Parse the command line; the physical-mode options without --mode physical,
     and combinations the decoder rejects, are argparse errors."""
-    from .device import phys_quant_args, phys_rule_args
+    from .device import phys_flags, phys_quant_args, phys_rule_args
     ap = build_parser()
     a = ap.parse_args(argv)
     if a.mode != "physical" and (a.cn_rule != "spa" or a.schedule != "flooding" or a.alpha is not None
@@ -189,12 +241,16 @@ def parse_args(argv=None):
         ap.error("--cn-rule, --schedule, --alpha and --beta need --mode physical")
     if a.mode != "physical" and (a.qbits is not None or a.llr_scale is not None):
         ap.error("--qbits and --llr-scale need --mode physical")
+    if a.layered_tile and (a.mode != "physical" or a.schedule != "layered"):
+        ap.error("--layered-tile needs --mode physical --schedule layered")
     if a.llr_scale is not None and a.qbits is None:
         ap.error("--llr-scale needs --qbits")
     a.llr_scale = 4.0 if a.llr_scale is None else a.llr_scale
     a.alpha = 0.75 if a.alpha is None else a.alpha
     a.beta = 0.5 if a.beta is None else a.beta
     try:
+        check_ira_mode(a.matrix, a.mode)
+        phys_flags(tile=a.layered_tile, schedule=a.schedule)
         phys_rule_args(a.cn_rule, a.schedule, a.alpha, a.beta)
         if a.qbits is not None:
             phys_quant_args(a.cn_rule, a.alpha, a.beta, a.qbits, a.llr_scale)
@@ -216,7 +272,8 @@ def main(argv=None):
     snrs = snr_grid(a.initial_snr, a.end_snr, a.step_snr)
     res, _ = simulate(a.matrix, snrs, a.blocks, a.iterations, seed=a.seed, nllr=a.normalized_llr,
                       device=local, rank=rank, world=world, allreduce=allreduce, mode=a.mode, cn_rule=a.cn_rule,
-                      schedule=a.schedule, alpha=a.alpha, beta=a.beta, qbits=a.qbits, llr_scale=a.llr_scale)
+                      schedule=a.schedule, alpha=a.alpha, beta=a.beta, qbits=a.qbits, llr_scale=a.llr_scale,
+                      layered_tile=a.layered_tile)
     if rank == 0:
         for sp in res.snr_points:
             print(f"SNR {sp.snr_db:.2f} dB  FER {sp.fer:.6f}  BER {sp.ber:.6e}  "

@@ -55,6 +55,9 @@ extern "C" {
                                    identity column's M = (0 + E) - E is 0 on every iteration) */
 #define LDPC_F_LAYERED_TILE 0x40u /* physical mode, LDPC_SCHED_LAYERED: the HBM tile kernels even if
                                      the state fits LDS (tests, A/B); LDPC_EINVAL with LDPC_SCHED_FLOODING */
+#define LDPC_F_QUANT_TILE 0x80u /* fixed-point entries (ldpc_phys_decode_q, ldpc_phys_mc_run_q): the HBM tile
+                                   kernels even if the state fits LDS (tests, A/B); LDPC_EINVAL on the
+                                   fp32 physical-mode entries */
 
 typedef struct ldpc_hstd ldpc_hstd;       /* standard-form parity-check matrix  */
 typedef struct ldpc_graph ldpc_graph;     /* H_std uploaded to one GPU          */
@@ -316,11 +319,14 @@ int ldpc_layers_build(int32_t m, int32_t n, const int32_t *row_ptr, const int32_
  * has Q = [5, -3, 31, 0], min1 = 0 at edge 3, min2 = 3, magnitudes
  * [0, 0, 0, (36 + 8) >> 4 = 2], parity 1: R = [0, 0, 0, -2].  With llr_scale 4,
  * llr 0.625 gives Lam -2 and llr 0.875 gives Lam -4 (both ties round to even).
- * A frame's state (int8 E, int16 L, int8 Lam) lives in LDS
- * (ldpc_phys_q_lds_bytes; n < 65535).  With LDPC_F_PHYS_HBM or LDPC_F_LAYERED_TILE, or on a graph
- * whose quantized state does not fit, the calls return LDPC_ERANGE;
- * LDPC_CN_SPA, a row of fewer than 2 edges, or a parameter out of range is
- * LDPC_EINVAL.  Every check runs before any device work.  The results equal a
+ * A frame's state (int8 E, int16 L, int8 Lam) lives in LDS when it fits
+ * (ldpc_phys_q_lds_bytes; n < 65535), else -- or with LDPC_F_QUANT_TILE -- in
+ * HBM, 64 frames per tile (csrc/phys_qtile.hip: any n, e.g. the DVB-S2 profile
+ * n = 64800; a temporary or the decoder's fp32 tile workspace holds it); both
+ * give the same integers.  LDPC_F_PHYS_HBM and LDPC_F_LAYERED_TILE select the
+ * fp32 tile kernels: on these entries they are LDPC_ERANGE, with or without
+ * LDPC_F_QUANT_TILE.  LDPC_CN_SPA, a row of fewer than 2 edges, or a parameter
+ * out of range is LDPC_EINVAL.  Every check runs before any device work.  The results equal a
  * numpy int32 restatement of these rules (tests/qminsum_ref.py).
  * LDPC_PHYS_Q_GRID=<workgroups> in the environment (read per launch) caps the
  * grid, so that one workgroup decodes many frames in sequence (tests, A/B). */
@@ -331,8 +337,10 @@ int ldpc_phys_decode_q(const ldpc_graph *g, int32_t batch, const double *llr, in
                        int32_t cn_rule, int32_t schedule, int32_t qbits, float llr_scale, int32_t param_q,
                        uint8_t *z_out, int32_t *conv_out, int32_t *status_out, int32_t *iters_out, int16_t *post_out,
                        void *stream);
-/* ldpc_phys_mc_run_ex on the same on-device frames (read as fp32 Lambda rows),
- * decoded in fixed point (same counters). */
+/* ldpc_phys_mc_run_ex on the same on-device frames (read as fp32 Lambda: rows
+ * for the LDS kernels, tiles for the HBM tile kernels), decoded in fixed point
+ * (same counters).  The tile path polls and compacts as ldpc_phys_mc_run's
+ * (LDPC_PHYS_COMPACT=0 switches the compaction off; the counters are the same). */
 int ldpc_phys_mc_run_q(ldpc_decoder *d_std, const ldpc_graph *g_phys, uint64_t seed, int32_t n_points,
                        const double *sigmas, int64_t frames_per_point, int64_t frame0, int32_t max_iter,
                        uint32_t flags, int32_t cn_rule, int32_t schedule, int32_t qbits, float llr_scale,
@@ -340,7 +348,8 @@ int ldpc_phys_mc_run_q(ldpc_decoder *d_std, const ldpc_graph *g_phys, uint64_t s
 /* The kernel ldpc_phys_decode_q runs: "phys_quant_reg_kernel" (flooding, on a
  * graph the register-index kernel has a shape for) or "phys_quant_kernel" (any
  * graph; the layered schedule; flooding with LDPC_PHYS_Q_REG=0 in the
- * environment); "" for a combination the decode rejects. */
+ * environment); on the HBM tiles "phys_qlayer_tile_kernel" (layered) or
+ * "phys_qcn_tile_kernel" (flooding); "" for a combination the decode rejects. */
 const char *ldpc_phys_kernel_name_q(const ldpc_graph *g, uint32_t flags, int32_t cn_rule, int32_t schedule,
                                     int32_t qbits);
 /* LDS bytes of a frame's quantized state under a schedule (-1: bad arguments). */

@@ -689,12 +689,14 @@ bool phys_use_lds(const DevGraph &P, uint32_t flags);
 
 const char *ldpc_phys_kernel_name(const ldpc_graph *g, uint32_t flags) {
     if (!g) return "";
+    if (flags & LDPC_F_QUANT_TILE) return "";  // the fixed-point entries' flag
     if (!phys_use_lds(g->dg, flags)) return "phys_cn_tile_kernel";
     return ldpc::phys_block_threads(g->dg) > 256 ? "phys_reg_kernel" : "phys_kernel";
 }
 
 const char *ldpc_phys_kernel_name_ex(const ldpc_graph *g, uint32_t flags, int32_t cn_rule, int32_t schedule) {
     if (!g || cn_rule < LDPC_CN_SPA || cn_rule > LDPC_CN_OMS) return "";
+    if (flags & LDPC_F_QUANT_TILE) return "";
     if (schedule == LDPC_SCHED_FLOODING) return (flags & LDPC_F_LAYERED_TILE) ? "" : ldpc_phys_kernel_name(g, flags);
     if (schedule != LDPC_SCHED_LAYERED || cn_rule == LDPC_CN_SPA || (flags & LDPC_F_PHYS_HBM)) return "";
     if ((flags & LDPC_F_LAYERED_TILE) || ldpc::phys_layered_lds_bytes(g->dg) > kLdsLimit)
@@ -1372,6 +1374,9 @@ int phys_rule(const char *fn, const ldpc_graph *g, uint32_t flags, int32_t cn_ru
                          fn, g->min_row_deg);
     if ((flags & LDPC_F_LAYERED_TILE) && schedule != LDPC_SCHED_LAYERED)
         return ldpc_fail(LDPC_EINVAL, "%s: LDPC_F_LAYERED_TILE needs LDPC_SCHED_LAYERED", fn);
+    if (flags & LDPC_F_QUANT_TILE)
+        return ldpc_fail(LDPC_EINVAL, "%s: LDPC_F_QUANT_TILE belongs to the fixed-point entries "
+                                      "(ldpc_phys_decode_q, ldpc_phys_mc_run_q)", fn);
     *rule = PhysRule{};
     rule->cn = cn_rule;
     rule->param = cn_rule == LDPC_CN_SPA ? 0.0f : param;
@@ -1733,6 +1738,12 @@ bool quant_fits(const ldpc_graph *g, bool layered) {
     return g->dg.n < 65535 && ldpc::phys_quant_lds_bytes(g->dg, quant_epad(g), layered) <= kLdsLimit;
 }
 
+// Whether the fixed-point entries run the HBM tile kernels (phys_qtile.hip): on
+// request, and for a graph whose quantized state does not fit LDS.
+bool quant_use_tile(const ldpc_graph *g, uint32_t flags, int32_t schedule) {
+    return (flags & LDPC_F_QUANT_TILE) || !quant_fits(g, schedule == LDPC_SCHED_LAYERED);
+}
+
 // The argument checks of the quantized entries; they touch no device.
 int quant_check(const char *fn, const ldpc_graph *g, uint32_t flags, int32_t cn_rule, int32_t schedule, int32_t qbits,
                 float llr_scale, int32_t param_q) {
@@ -1756,12 +1767,8 @@ int quant_check(const char *fn, const ldpc_graph *g, uint32_t flags, int32_t cn_
         return ldpc_fail(LDPC_EINVAL, "%s: min-sum needs every check row to have at least 2 edges (a row has %d)",
                          fn, g->min_row_deg);
     if (flags & (LDPC_F_PHYS_HBM | LDPC_F_LAYERED_TILE))
-        return ldpc_fail(LDPC_ERANGE, "%s: the fixed-point decoder runs only with a frame's state in LDS "
-                                      "(not with LDPC_F_PHYS_HBM or LDPC_F_LAYERED_TILE)", fn);
-    if (!quant_fits(g, schedule == LDPC_SCHED_LAYERED))
-        return ldpc_fail(LDPC_ERANGE, "%s: the graph's quantized state (%lld bytes, n = %d) does not fit LDS", fn,
-                         (long long)ldpc::phys_quant_lds_bytes(g->dg, quant_epad(g),
-                                                               schedule == LDPC_SCHED_LAYERED), g->dg.n);
+        return ldpc_fail(LDPC_ERANGE, "%s: LDPC_F_PHYS_HBM and LDPC_F_LAYERED_TILE select the fp32 tile kernels; "
+                                      "the fixed-point decoder's HBM path is LDPC_F_QUANT_TILE", fn);
     return LDPC_OK;
 }
 
@@ -1813,14 +1820,17 @@ int graph_quant_tab(const ldpc_graph *g, ldpc::QuantTab *tab) {
 }
 
 // Fill the kernel's rule (device tables: call with g's device current, after quant_check).
-int quant_rule(const ldpc_graph *g, int32_t cn_rule, int32_t schedule, int32_t qbits, float llr_scale,
+int quant_rule(const ldpc_graph *g, uint32_t flags, int32_t cn_rule, int32_t schedule, int32_t qbits, float llr_scale,
                int32_t param_q, ldpc::QuantRule *rule) {
     *rule = ldpc::QuantRule{};
     rule->cn = cn_rule;
     rule->qbits = qbits;
     rule->scale = llr_scale;
     rule->param_q = param_q;
-    if (int rc = graph_quant_tab(g, &rule->tab)) return rc;
+    rule->tile = quant_use_tile(g, flags, schedule);
+    // the tile path reads the graph's CSR / CSC itself: no padded table
+    if (!rule->tile)
+        if (int rc = graph_quant_tab(g, &rule->tab)) return rc;
     if (schedule == LDPC_SCHED_LAYERED) {
         PhysRule pr;
         if (int rc = graph_layers(g, &pr)) return rc;
@@ -1828,6 +1838,7 @@ int quant_rule(const ldpc_graph *g, int32_t cn_rule, int32_t schedule, int32_t q
         rule->layer_rows = pr.layer_rows;
         rule->n_layers = pr.n_layers;
         rule->max_layer = pr.max_layer;
+        rule->h_layer_ptr = pr.h_layer_ptr;
     }
     return LDPC_OK;
 }
@@ -1843,16 +1854,140 @@ int phys_quant_max_grid() {
     return INT_MAX;
 }
 
+// The fixed-point state on the tiles, in the bytes of the fp32 tile path's
+// workspace (ensure_phys_tile; nothing more is allocated): E8 in pE (a quarter
+// of it), L16 in the first half of pL and Lam8 in its third quarter.  pLam
+// stays free for the generator's fp32 Lambda tiles, which the load reads.
+ldpc::QTile quant_tile(ldpc_decoder *d, const ldpc::QuantRule &rule) {
+    const size_t cap = (size_t)d->cap_tiles * kTile, n = (size_t)d->g->dg.n;
+    ldpc::QTile qt{};
+    qt.E = reinterpret_cast<int8_t *>(d->pE);
+    qt.L = reinterpret_cast<int16_t *>(d->pL);
+    qt.Lam = reinterpret_cast<int8_t *>(d->pL) + 2 * cap * n;
+    qt.bad = d->pbad;
+    qt.cap = (int)cap;
+    qt.qmax = (1 << (rule.qbits - 1)) - 1;
+    qt.pmax = (1 << (rule.qbits + 1)) - 1;
+    qt.param_q = rule.param_q;
+    qt.scale = rule.scale;
+    return qt;
+}
+
+// Decode the frames bound in d->st on graph P with the fixed-point tile
+// kernels (phys_qtile.hip); lam32: the generator's fp32 Lambda tiles, or null:
+// the channel LLRs in d->ch.  The launches, the polls (it < 4 and every 4th
+// iteration) and, with ctr, the compaction are phys_tile_decode's and
+// phys_tile_decode_layered's; the exits run on the device every iteration, so
+// no result depends on a poll.
+int phys_qtile_decode(ldpc_decoder *d, const DevGraph &P, int max_iter, const float *lam32, hipStream_t s,
+                      unsigned long long *ctr, const ldpc::QuantRule &rule) {
+    if (int rc = ensure_pactive(d, max_iter)) return rc;
+    DevState st = d->st;  // st.ntiles shrinks with each compaction
+    const ldpc::QTile qt = quant_tile(d, rule);
+    const bool layered = rule.layer_ptr != nullptr;
+    const int cap = d->cap_tiles * kTile;
+    const bool compact = phys_compact_enabled();
+    HIP_TRY(hipMemsetAsync(d->pactive, 0, sizeof(int) * 2 * max_iter, s));
+    HIP_TRY(ldpc::launch_phys_qtile_init(P, st, qt, lam32, !layered, s));
+    for (int it = 0; it < max_iter; ++it) {
+        if (layered) {
+            HIP_TRY(timed(d, LDPC_K_PHYS_CN, s, [&] {
+                for (int l = 0; l < rule.n_layers; ++l) {
+                    const int lbeg = rule.h_layer_ptr[l], lrows = rule.h_layer_ptr[l + 1] - lbeg;
+                    if (hipError_t e = ldpc::launch_phys_qlayer_tile(P, st, qt, rule.cn, it, lbeg, lrows,
+                                                                     rule.layer_rows, s))
+                        return e;
+                }
+                return hipSuccess;
+            }));
+            HIP_TRY(timed(d, LDPC_K_PHYS_VN, s,
+                          [&] { return ldpc::launch_phys_qlayer_exit(P, st, qt, it, d->pactive, max_iter, s); }));
+        } else {
+            HIP_TRY(timed(d, LDPC_K_PHYS_CN, s, [&] { return ldpc::launch_phys_qtile_cn(P, st, qt, rule.cn, it, s); }));
+            HIP_TRY(timed(d, LDPC_K_PHYS_VN, s,
+                          [&] { return ldpc::launch_phys_qtile_vn(P, st, qt, it, d->pactive, max_iter, s); }));
+        }
+        if (it + 1 < max_iter && (it < 4 || (it + 1) % 4 == 0)) {
+            // flooding, iterations 1 and 2: the frames whose posterior satisfies
+            // every check stop now, not after the next check sweep (phys_tile_decode)
+            if (!layered && (it == 1 || it == 2))
+                HIP_TRY(timed(d, LDPC_K_PHYS_VN, s, [&] {
+                    return ldpc::launch_phys_qtile_early_exit(P, st, qt, it, d->pactive, max_iter, s);
+                }));
+            int running[2] = {0, 0};  // tiles, frames
+            HIP_TRY(hipMemcpyAsync(&running[0], d->pactive + it, sizeof(int), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(&running[1], d->pactive + max_iter + it, sizeof(int), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            if (running[0] == 0) break;  // every frame has stopped
+            const int nt = (running[1] + kTile - 1) / kTile;
+            if (ctr && compact && nt < st.ntiles && 4 * (int64_t)running[1] <= (int64_t)st.ntiles * kTile) {
+                if (!d->cpairs && dev_alloc(&d->cpairs, 1 + 2 * (size_t)cap)) return LDPC_ENOMEM;
+                HIP_TRY(timed(d, LDPC_K_COUNT, s, [&] { return ldpc::launch_phys_qtile_count(P, st, qt, ctr, s); }));
+                HIP_TRY(ldpc::launch_phys_qtile_compact(P, st, qt, !layered, nt, cap, d->cpairs, s));
+                st.ntiles = nt;
+            }
+        }
+    }
+    // flooding: the frames that converge on the last iteration (the layered exit stops every frame itself)
+    if (!layered) HIP_TRY(ldpc::launch_phys_qtile_final(P, st, qt, max_iter, s));
+    return LDPC_OK;
+}
+
+// ldpc_phys_decode_q on the tiles: chunks of 1024 frames through a temporary
+// workspace, staging as phys_decode_tile, int16 posteriors.
+int phys_decode_qtile(const ldpc_graph *g, int32_t batch, const double *llr, int32_t max_iter, uint32_t flags,
+                      uint8_t *z_out, int32_t *conv_out, int32_t *status_out, int32_t *iters_out, int16_t *post_out,
+                      hipStream_t s, const ldpc::QuantRule &rule) {
+    const DevGraph &G = g->dg;
+    const bool dev_ptrs = flags & LDPC_F_DEVICE_PTRS;
+    const int chunk = std::min<int>(batch, 1024);
+    ldpc_decoder *d = nullptr;
+    if (int rc = ldpc_decoder_create(g, chunk, &d)) return rc;
+    struct Free {
+        ldpc_decoder *d;
+        ~Free() { ldpc_decoder_destroy(d); }
+    } guard{d};
+    if (int rc = ensure_phys_tile(d, G)) return rc;
+    const size_t n = (size_t)G.n;
+    for (int start = 0; start < batch; start += chunk) {
+        const int cnt = std::min(chunk, batch - start);
+        state_bind(d, (cnt + kTile - 1) / kTile, cnt);
+        const DevState &st = d->st;
+        const double *src = llr + (size_t)start * n;
+        if (!dev_ptrs) {
+            HIP_TRY(hipMemcpyAsync(d->llr_stage, src, sizeof(double) * cnt * n, hipMemcpyHostToDevice, s));
+            src = d->llr_stage;
+        }
+        HIP_TRY(ldpc::launch_load_llr(G, st, src, s));
+        if (int rc = phys_qtile_decode(d, G, max_iter, nullptr, s, nullptr, rule)) return rc;
+        uint8_t *zd = z_out ? (dev_ptrs ? z_out + (size_t)start * n : d->z_stage) : nullptr;
+        int16_t *pd = post_out ? (dev_ptrs ? post_out + (size_t)start * n : (int16_t *)d->post_stage) : nullptr;
+        HIP_TRY(ldpc::launch_phys_qtile_out(G, st, quant_tile(d, rule), zd, pd, s));
+        const hipMemcpyKind kind = dev_ptrs ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        if (conv_out) HIP_TRY(hipMemcpyAsync(conv_out + start, st.conv, sizeof(int) * cnt, kind, s));
+        if (status_out) HIP_TRY(hipMemcpyAsync(status_out + start, st.status, sizeof(int) * cnt, kind, s));
+        if (iters_out) HIP_TRY(hipMemcpyAsync(iters_out + start, st.iters, sizeof(int) * cnt, kind, s));
+        if (!dev_ptrs) {
+            if (z_out) HIP_TRY(hipMemcpyAsync(z_out + (size_t)start * n, zd, cnt * n, hipMemcpyDeviceToHost, s));
+            if (post_out)
+                HIP_TRY(hipMemcpyAsync(post_out + (size_t)start * n, pd, sizeof(int16_t) * cnt * n,
+                                       hipMemcpyDeviceToHost, s));
+        }
+        HIP_TRY(hipStreamSynchronize(s));  // staging and workspace are reused / freed
+    }
+    return LDPC_OK;
+}
+
 }  // namespace
 
 const char *ldpc_phys_kernel_name_q(const ldpc_graph *g, uint32_t flags, int32_t cn_rule, int32_t schedule,
                                     int32_t qbits) {
     if (!g || (cn_rule != LDPC_CN_NMS && cn_rule != LDPC_CN_OMS) ||
         (schedule != LDPC_SCHED_FLOODING && schedule != LDPC_SCHED_LAYERED) || qbits < 4 || qbits > 8 ||
-        g->min_row_deg < 2 || (flags & (LDPC_F_PHYS_HBM | LDPC_F_LAYERED_TILE)) ||
-        !quant_fits(g, schedule == LDPC_SCHED_LAYERED))
+        g->min_row_deg < 2 || (flags & (LDPC_F_PHYS_HBM | LDPC_F_LAYERED_TILE)))
         return "";
     const bool layered = schedule == LDPC_SCHED_LAYERED;
+    if (quant_use_tile(g, flags, schedule)) return layered ? "phys_qlayer_tile_kernel" : "phys_qcn_tile_kernel";
     return ldpc::phys_quant_reg_shape(g->dg, quant_epad(g), layered) >= 0 ? "phys_quant_reg_kernel" : "phys_quant_kernel";
 }
 
@@ -1873,8 +2008,11 @@ int ldpc_phys_decode_q(const ldpc_graph *g, int32_t batch, const double *llr, in
     if (batch == 0) return LDPC_OK;
     DeviceGuard dg(g->device);
     ldpc::QuantRule rule;
-    if (int rc = quant_rule(g, cn_rule, schedule, qbits, llr_scale, param_q, &rule)) return rc;
+    if (int rc = quant_rule(g, flags, cn_rule, schedule, qbits, llr_scale, param_q, &rule)) return rc;
     hipStream_t s = (hipStream_t)stream;
+    if (rule.tile)
+        return phys_decode_qtile(g, batch, llr, max_iter, flags, z_out, conv_out, status_out, iters_out, post_out, s,
+                                 rule);
     const DevGraph &G = g->dg;
     const size_t n = (size_t)G.n, B = (size_t)batch;
     auto launch = [&](const double *in, uint8_t *z, int *conv, int *status, int *iters, int16_t *post) {
@@ -1933,8 +2071,10 @@ int ldpc_phys_mc_run_q(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int
     if (int rc = quant_check(fn, gp, flags, cn_rule, schedule, qbits, llr_scale, param_q)) return rc;
     DeviceGuard dg(d->g->device);
     ldpc::QuantRule rule;
-    if (int rc = quant_rule(gp, cn_rule, schedule, qbits, llr_scale, param_q, &rule)) return rc;
+    if (int rc = quant_rule(gp, flags, cn_rule, schedule, qbits, llr_scale, param_q, &rule)) return rc;
     hipStream_t s = (hipStream_t)stream;
+    if (rule.tile)
+        if (int rc = ensure_phys_tile(d, P)) return rc;
     if (int rc = ensure_pbits(d, G)) return rc;
     const int need = n_points * LDPC_MC_NCOUNT;
     if (d->counters_cap < need) {
@@ -1952,11 +2092,18 @@ int ldpc_phys_mc_run_q(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int
             const int cnt = (int)std::min<int64_t>(cap, frames_per_point - start);
             state_bind(d, (cnt + kTile - 1) / kTile, cnt);
             const DevState st = d->st;
-            float *rows = (float *)d->llr_stage;  // the frames as fp32 Lambda rows, as phys_mc_any's LDS path
+            // frames as fp32 Lambda: tiles (pLam) for the HBM tile decoder, rows for the LDS decoder
+            float *rows = (float *)d->llr_stage;
             HIP_TRY(timed(d, LDPC_K_GEN, s, [&] {
                 return ldpc::launch_frames(G, st, phys_tile(d), seed, p, sigmas[p], frame0 + start,
-                                           ldpc::kFramesRowLambda, rows, s);
+                                           rule.tile ? ldpc::kFramesTileLambda : ldpc::kFramesRowLambda, rows, s);
             }));
+            if (rule.tile) {
+                if (int rc = phys_qtile_decode(d, P, max_iter, d->pLam, s, ctr, rule)) return rc;
+                HIP_TRY(timed(d, LDPC_K_COUNT, s,
+                              [&] { return ldpc::launch_phys_qtile_count(P, st, quant_tile(d, rule), ctr, s); }));
+                continue;
+            }
             HIP_TRY(timed(d, LDPC_K_PHYS, s, [&] {
                 return ldpc::launch_phys_quant(P, nullptr, rows, cnt, max_iter, nullptr, nullptr, nullptr, nullptr,
                                                nullptr, st.ubits, ctr, phys_quant_max_grid(), s, rule);

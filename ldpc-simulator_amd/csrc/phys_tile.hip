@@ -38,6 +38,7 @@
 
 #include "phys_common.h"
 #include "phys_math.h"
+#include "phys_tile_common.h"
 #include "spa_device.h"
 
 namespace ldpc {
@@ -51,28 +52,7 @@ __device__ __forceinline__ float ld_e32(const float *p) { return __builtin_nonte
 __device__ __forceinline__ void st_e32(float *p, float v) { __builtin_nontemporal_store(v, p); }
 
 
-constexpr int kRowsPerWave = 4;
-constexpr int kColsPerWave = 8;
 constexpr int kVnBatch = 4;  // columns per batch of phys_vn_tile's batched loads (2 / 8: same or slower)
-
-__device__ __forceinline__ int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// Work item i = (tile, part).  Blocks b and b+8 run on the same XCD; the grid
-// is a multiple of 8 and block b takes items b, b+G, b+2G, ... so every item
-// of a block -- and every part of one tile -- has the same i%8 = tile%8: a
-// tile's L rows stay in one XCD's L2.  A grid of a few thousand blocks makes
-// a launch over finished tiles cost a few microseconds, not one block per item.
-__device__ __forceinline__ void xcd_item(int i, int per_tile, int &tile, int &part) {
-    const int slot = i >> 3;
-    tile = (slot / per_tile) * 8 + (i & 7);
-    part = slot % per_tile;
-}
 
 // ------------------------------------------------------- tile decoder
 __global__ void phys_tile_init_kernel(DevGraph g, DevState st, PhysTile pt, int convert) {
@@ -657,11 +637,6 @@ __global__ __launch_bounds__(64) void phys_layer_exit_kernel(DevState st, PhysTi
         }
     }
 }
-
-inline unsigned grid_for(size_t total, int block) { return (unsigned)((total + block - 1) / block); }
-inline unsigned xcd_items(int ntiles, int per_tile) { return (unsigned)(((ntiles + 7) / 8) * 8 * per_tile); }
-// 256 CUs x 16 blocks of 4 waves (a multiple of 8, see xcd_item)
-inline unsigned stride_grid(int items) { return (unsigned)std::min(items, 4096); }
 
 }  // namespace
 

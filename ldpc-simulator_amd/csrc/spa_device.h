@@ -246,7 +246,9 @@ struct QuantRule {
     const int *layer_rows = nullptr;
     int n_layers = 0;
     int max_layer = 0;
-    QuantTab tab;
+    QuantTab tab;                   // the LDS kernels' layout; unset on the tile path
+    bool tile = false;              // the HBM tile kernels (phys_qtile.hip), not the LDS kernels
+    const int *h_layer_ptr = nullptr;  // as PhysRule (the tile path sizes a layer's launch by it)
 };
 size_t phys_quant_lds_bytes(const DevGraph &g, int epad, bool layered);
 // >= 0: the flooding decoder runs phys_quant_reg_kernel (indices in registers), else phys_quant_kernel
@@ -300,6 +302,44 @@ hipError_t launch_phys_tile_out(const DevGraph &g, const DevState &st, const Phy
                                 hipStream_t s);
 hipError_t launch_phys_tile_count(const DevGraph &g, const DevState &st, const PhysTile &pt,
                                   unsigned long long *ctr, hipStream_t s);
+
+// fixed-point min-sum with the state in HBM (phys_qtile.hip): the tile layout
+// and the per-frame state (DevState, bad flags) of phys_tile.hip, the integers
+// of phys_quant.hip.  One byte per message and two per posterior.
+struct QTile {
+    int8_t *E;     // [tile][nnz][64] check->variable messages, CSR edge order
+    int16_t *L;    // [tile][n][64] posteriors (L < 0 -> bit 1)
+    int8_t *Lam;   // [tile][n][64] quantized Lambda, flooding only
+    int *bad;      // [2][cap] row-syndrome flags, by iteration parity (layered: slot 0)
+    int cap;       // frames of capacity (stride of bad)
+    int qmax, pmax, param_q;
+    float scale;   // llr_scale
+};
+// The contract's load: Lam = quantized lam32 * scale (fp32 Lambda tiles of the
+// frame generator) or, lam32 null, of -(float)st.ch * scale; L = Lam (Lam kept
+// only with `flooding`); per-frame state as launch_phys_tile_init.
+hipError_t launch_phys_qtile_init(const DevGraph &g, const DevState &st, const QTile &qt, const float *lam32,
+                                  bool flooding, hipStream_t s);
+// one layer of the layered schedule (as launch_phys_layer_tile); cn kCnNms / kCnOms
+hipError_t launch_phys_qlayer_tile(const DevGraph &g, const DevState &st, const QTile &qt, int cn, int it, int lbeg,
+                                   int lrows, const int *layer_rows, hipStream_t s);
+// layered: syndrome of b = (L < 0) and the exits of iteration it (as launch_phys_layer_exit)
+hipError_t launch_phys_qlayer_exit(const DevGraph &g, const DevState &st, const QTile &qt, int it, int *active_count,
+                                   int max_iter, hipStream_t s);
+// flooding: check sweep, variable sweep, the early syndrome + exits, and the last syndrome + final
+hipError_t launch_phys_qtile_cn(const DevGraph &g, const DevState &st, const QTile &qt, int cn, int it, hipStream_t s);
+hipError_t launch_phys_qtile_vn(const DevGraph &g, const DevState &st, const QTile &qt, int it, int *active_count,
+                                int max_iter, hipStream_t s);
+hipError_t launch_phys_qtile_early_exit(const DevGraph &g, const DevState &st, const QTile &qt, int it,
+                                        int *active_count, int max_iter, hipStream_t s);
+hipError_t launch_phys_qtile_final(const DevGraph &g, const DevState &st, const QTile &qt, int max_iter,
+                                   hipStream_t s);
+hipError_t launch_phys_qtile_out(const DevGraph &g, const DevState &st, const QTile &qt, uint8_t *z, int16_t *post,
+                                 hipStream_t s);
+hipError_t launch_phys_qtile_count(const DevGraph &g, const DevState &st, const QTile &qt, unsigned long long *ctr,
+                                   hipStream_t s);
+hipError_t launch_phys_qtile_compact(const DevGraph &g, const DevState &st, const QTile &qt, bool flooding, int nt,
+                                     int cap, int *pairs, hipStream_t s);
 
 // --- Philox4x32-10 (Salmon et al., SC'11), shared by host tests and device ---
 __host__ __device__ inline void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {

@@ -29,6 +29,7 @@ LDPC_F_PHYS_HBM = 0x8
 LDPC_F_SPLIT = 0x10
 LDPC_F_TEST_ZERO = 0x20  # test only: frame-source erasures (include/ldpc_hip.h)
 LDPC_F_LAYERED_TILE = 0x40  # layered schedule on the HBM tile kernels even if the state fits LDS
+LDPC_F_QUANT_TILE = 0x80  # fixed-point decoder on the HBM tile kernels even if the state fits LDS
 LDPC_MC_NCOUNT = 7
 LDPC_EINVAL = -22  # include/ldpc_hip.h error codes used on the Python side
 LDPC_ERANGE = -34

@@ -19,7 +19,7 @@ from scipy import sparse
 
 from . import _lib
 from ._lib import (LDPC_EINVAL, LDPC_ERANGE, LDPC_F_DEVICE_PTRS, LDPC_F_LAYERED_TILE, LDPC_F_NLLR, LDPC_F_PHYS_HBM,
-                   LDPC_F_SPLIT, LDPC_F_STATIC, LDPC_MC_NCOUNT, LdpcError, as_i32, check)
+                   LDPC_F_QUANT_TILE, LDPC_F_SPLIT, LDPC_F_STATIC, LDPC_MC_NCOUNT, LdpcError, as_i32, check)
 
 
 def _csr_arrays(H):
@@ -127,13 +127,22 @@ def phys_rule_args(cn="spa", schedule="flooding", alpha=0.75, beta=0.5):
     return CN_RULES[cn], SCHEDULES[schedule], {"spa": 0.0, "nms": alpha, "oms": beta}[cn]
 
 
-def phys_flags(hbm=False, tile=False, schedule="flooding"):
+def phys_flags(hbm=False, tile=False, schedule="flooding", qtile=False):
     """The physical-mode flags: hbm forces the flooding HBM tile path, tile the
-    layered schedule's (LDPC_F_LAYERED_TILE).  tile without
-    schedule="layered" raises ValueError -- before any device call."""
+    layered schedule's (LDPC_F_LAYERED_TILE), qtile the fixed-point decoder's
+    (LDPC_F_QUANT_TILE; either schedule).  tile without schedule="layered"
+    raises ValueError -- before any device call."""
     if tile and schedule != "layered":
         raise ValueError(f"tile=True needs schedule='layered', got {schedule!r}")
-    return (LDPC_F_PHYS_HBM if hbm else 0) | (LDPC_F_LAYERED_TILE if tile else 0)
+    return (LDPC_F_PHYS_HBM if hbm else 0) | (LDPC_F_LAYERED_TILE if tile else 0) | \
+        (LDPC_F_QUANT_TILE if qtile else 0)
+
+
+def _need_qbits(qtile, qbits):
+    """qtile selects the fixed-point decoder's tile kernels: without qbits it
+    has no meaning (ValueError -- before any device call)."""
+    if qtile and qbits is None:
+        raise ValueError("qtile=True needs qbits (the fixed-point decoder)")
 
 
 def phys_quant_args(cn, alpha=0.75, beta=0.5, qbits=6, llr_scale=4.0):
@@ -164,10 +173,12 @@ def phys_quant_args(cn, alpha=0.75, beta=0.5, qbits=6, llr_scale=4.0):
     return qbits, llr_scale, param_q
 
 
-def phys_kernel_name(graph, hbm=False, cn="spa", schedule="flooding", qbits=None, llr_scale=4.0, tile=False):
+def phys_kernel_name(graph, hbm=False, cn="spa", schedule="flooding", qbits=None, llr_scale=4.0, tile=False,
+                     qtile=False):
     """Measurement label: the kernel phys_decode runs for these options."""
+    _need_qbits(qtile, qbits)
     rule, sched, _ = phys_rule_args(cn, schedule)
-    flags = phys_flags(hbm, tile, schedule)
+    flags = phys_flags(hbm, tile, schedule, qtile)
     if qbits is not None:
         qbits, _, _ = phys_quant_args(cn, qbits=qbits, llr_scale=llr_scale)
         return _lib.gpu().ldpc_phys_kernel_name_q(graph.handle, flags, rule, sched, qbits).decode()
@@ -175,7 +186,7 @@ def phys_kernel_name(graph, hbm=False, cn="spa", schedule="flooding", qbits=None
 
 
 def phys_decode(graph, llr, max_iter, post=False, hbm=False, cn="spa", schedule="flooding", alpha=0.75, beta=0.5,
-                ex=False, qbits=None, llr_scale=4.0, tile=False):
+                ex=False, qbits=None, llr_scale=4.0, tile=False, qtile=False):
     """Physical-mode decode of [B, n] LLRs on a sparse graph (H[:, perm]).
 
     State in LDS when a frame fits, else in HBM (hbm=True forces HBM).
@@ -188,9 +199,12 @@ def phys_decode(graph, llr, max_iter, post=False, hbm=False, cn="spa", schedule=
     qbits=4..8: the fixed-point min-sum decoder (ldpc_phys_decode_q;
     phys_quant_args turns alpha / beta into its integers) on LLRs scaled by
     llr_scale; post is then the integer posterior, int16, in units of
-    1 / llr_scale.  qbits=None: the fp32 decoders, llr_scale unused."""
+    1 / llr_scale.  Its state is in LDS when it fits, else on the HBM tiles
+    (qtile=True forces them, either schedule; it needs qbits).  qbits=None:
+    the fp32 decoders, llr_scale unused."""
+    _need_qbits(qtile, qbits)
     rule, sched, param = phys_rule_args(cn, schedule, alpha, beta)
-    flags = phys_flags(hbm, tile, schedule)
+    flags = phys_flags(hbm, tile, schedule, qtile)
     if qbits is not None:
         qbits, llr_scale, param_q = phys_quant_args(cn, alpha, beta, qbits, llr_scale)
     llr = np.ascontiguousarray(np.atleast_2d(np.asarray(llr, dtype=np.float64)))
@@ -341,7 +355,7 @@ class Decoder:
         return out
 
     def phys_mc_run(self, phys_graph, seed, sigmas, frames_per_point, frame0, max_iter, hbm=False, cn="spa",
-                    schedule="flooding", alpha=0.75, beta=0.5, qbits=None, llr_scale=4.0, tile=False):
+                    schedule="flooding", alpha=0.75, beta=0.5, qbits=None, llr_scale=4.0, tile=False, qtile=False):
         """Physical mode (§8 f4): same on-device frames, decoded on the sparse graph.
 
         This decoder's graph is the code's H_std (frame source) or, for an IRA
@@ -349,9 +363,10 @@ class Decoder:
         tile=True the layered schedule's (it needs schedule="layered").
         cn / schedule / alpha / beta as phys_decode (the defaults are
         ldpc_phys_mc_run, anything else ldpc_phys_mc_run_ex); qbits /
-        llr_scale as phys_decode (ldpc_phys_mc_run_q)."""
+        llr_scale / qtile as phys_decode (ldpc_phys_mc_run_q)."""
+        _need_qbits(qtile, qbits)
         rule, sched, param = phys_rule_args(cn, schedule, alpha, beta)
-        flags = phys_flags(hbm, tile, schedule)
+        flags = phys_flags(hbm, tile, schedule, qtile)
         if qbits is not None:
             qbits, llr_scale, param_q = phys_quant_args(cn, alpha, beta, qbits, llr_scale)
         sig = np.ascontiguousarray(np.asarray(sigmas, dtype=np.float64))

@@ -116,7 +116,7 @@ def decoder_type(cn_rule="spa", schedule="flooding", qbits=None):
 
 def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65536, device=0,
              rank=0, world=1, allreduce=None, matrix_path="", mode="parity", cn_rule="spa", schedule="flooding",
-             alpha=0.75, beta=0.5, qbits=None, llr_scale=4.0, layered_tile=False):
+             alpha=0.75, beta=0.5, qbits=None, llr_scale=4.0, layered_tile=False, quant_tile=False):
     """Full sweep on this process's GPU -> SimulationResult (reference schema).
 
     mode "parity" is the reference's decoder on H_std; "physical" decodes the
@@ -127,7 +127,8 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
     (device.phys_quant_args); it needs mode="physical" and a min-sum rule.
     layered_tile runs the layered schedule on the HBM tile kernels even where
     the state fits LDS (it needs schedule="layered"; a code too large for LDS
-    takes them anyway).  matrix may name an IRA code (IRA_CODES): physical
+    takes them anyway); quant_tile does the same for the fixed-point decoder
+    (it needs qbits; either schedule).  matrix may name an IRA code (IRA_CODES): physical
     mode only, the graph itself is the frame source."""
     from .code import EncoderDecoderData, load_committed_code
     from .device import Decoder, Graph, phys_flags, phys_quant_args, phys_rule_args
@@ -140,14 +141,16 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
         if mode != "physical":
             raise ValueError("qbits needs mode='physical'")
         phys_quant_args(cn_rule, alpha, beta, qbits, llr_scale)
-    phys_flags(tile=layered_tile, schedule=schedule)
+    elif quant_tile:
+        raise ValueError("quant_tile needs qbits (the fixed-point decoder)")
+    phys_flags(tile=layered_tile, schedule=schedule, qtile=quant_tile)
     check_ira_mode(matrix, mode)
     t0 = time.time()
     if isinstance(matrix, str) and matrix in IRA_CODES:
         from . import ira
         return _simulate_graph(getattr(ira, IRA_CODES[matrix])(), matrix, t0, snrs, blocks, max_iter, seed, chunk,
                                device, rank, world, allreduce, matrix_path, cn_rule, schedule, alpha, beta, qbits,
-                               llr_scale, layered_tile)
+                               llr_scale, layered_tile, quant_tile)
     if isinstance(matrix, EncoderDecoderData):
         edd = matrix
     elif isinstance(matrix, str) and os.path.exists(matrix):
@@ -162,7 +165,8 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
 
         def counter_fn(sigmas, cnt, frame0):
             return dec.phys_mc_run(gp, seed, sigmas, cnt, frame0, max_iter, cn=cn_rule, schedule=schedule,
-                                   alpha=alpha, beta=beta, qbits=qbits, llr_scale=llr_scale, tile=layered_tile)
+                                   alpha=alpha, beta=beta, qbits=qbits, llr_scale=llr_scale, tile=layered_tile,
+                                   qtile=quant_tile)
     ctr = run_sweep(dec, snrs, blocks, max_iter, seed=seed, nllr=nllr, rank=rank, world=world,
                     allreduce=allreduce, counter_fn=counter_fn)
     pts = point_results(ctr, edd._k, snrs, matrix_path=matrix_path or str(matrix), max_iter=max_iter)
@@ -176,7 +180,7 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
 
 
 def _simulate_graph(H, name, t0, snrs, blocks, max_iter, seed, chunk, device, rank, world, allreduce, matrix_path,
-                    cn_rule, schedule, alpha, beta, qbits, llr_scale, layered_tile):
+                    cn_rule, schedule, alpha, beta, qbits, llr_scale, layered_tile, quant_tile=False):
     """simulate() in physical mode on an IRA graph H: one graph, the decoder's
     frame source and the graph it decodes on (as bench.py's config 5)."""
     from .device import Decoder, Graph
@@ -187,7 +191,7 @@ def _simulate_graph(H, name, t0, snrs, blocks, max_iter, seed, chunk, device, ra
 
     def counter_fn(sigmas, cnt, frame0):
         return dec.phys_mc_run(g, seed, sigmas, cnt, frame0, max_iter, cn=cn_rule, schedule=schedule, alpha=alpha,
-                               beta=beta, qbits=qbits, llr_scale=llr_scale, tile=layered_tile)
+                               beta=beta, qbits=qbits, llr_scale=llr_scale, tile=layered_tile, qtile=quant_tile)
     ctr = run_sweep(dec, snrs, blocks, max_iter, seed=seed, rank=rank, world=world, allreduce=allreduce,
                     counter_fn=counter_fn)
     pts = point_results(ctr, k, snrs, matrix_path=matrix_path or name, max_iter=max_iter)
@@ -227,6 +231,8 @@ def build_parser():
                     help="physical mode, min-sum rules: fixed-point decoder with messages of 4..8 bits")
     ap.add_argument("--llr-scale", type=float, default=None,
                     help="with --qbits: quantizer steps per unit of LLR (default 4)")
+    ap.add_argument("--quant-tile", action="store_true",
+                    help="with --qbits: the HBM tile kernels even where the quantized state fits LDS")
     return ap
 
 
@@ -245,6 +251,8 @@ def parse_args(argv=None):
         ap.error("--layered-tile needs --mode physical --schedule layered")
     if a.llr_scale is not None and a.qbits is None:
         ap.error("--llr-scale needs --qbits")
+    if a.quant_tile and (a.mode != "physical" or a.qbits is None):
+        ap.error("--quant-tile needs --mode physical --qbits")
     a.llr_scale = 4.0 if a.llr_scale is None else a.llr_scale
     a.alpha = 0.75 if a.alpha is None else a.alpha
     a.beta = 0.5 if a.beta is None else a.beta
@@ -273,7 +281,7 @@ def main(argv=None):
     res, _ = simulate(a.matrix, snrs, a.blocks, a.iterations, seed=a.seed, nllr=a.normalized_llr,
                       device=local, rank=rank, world=world, allreduce=allreduce, mode=a.mode, cn_rule=a.cn_rule,
                       schedule=a.schedule, alpha=a.alpha, beta=a.beta, qbits=a.qbits, llr_scale=a.llr_scale,
-                      layered_tile=a.layered_tile)
+                      layered_tile=a.layered_tile, quant_tile=a.quant_tile)
     if rank == 0:
         for sp in res.snr_points:
             print(f"SNR {sp.snr_db:.2f} dB  FER {sp.fer:.6f}  BER {sp.ber:.6e}  "

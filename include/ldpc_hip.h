@@ -32,7 +32,8 @@ extern "C" {
 #endif
 
 #define LDPC_ABI_VERSION 5  /* 5: LDPC_F_TEST_ZERO + ldpc_rare_rows_read (4: profile kinds LDPC_K_NKINDS 11);
-                             * ldpc_fixed_point_read was added under 5: an addition only, nothing else changed */
+                             * ldpc_fixed_point_read was added under 5: an addition only, nothing else changed;
+                             * likewise ldpc_mc_stats_enable / ldpc_mc_stats_read: new symbols, the version stays 5 */
 
 /* error codes */
 #define LDPC_OK 0
@@ -391,6 +392,37 @@ int ldpc_rare_rows_read(ldpc_decoder *d, int64_t *out);
  * frame-passes they did not execute.  LDPC_FIXED_POINT=0 (environment, read
  * per launch) switches the exit off; results are identical either way. */
 int ldpc_fixed_point_read(ldpc_decoder *d, int64_t *out);
+
+/* ------------------------------------------- Monte-Carlo statistics
+ * Per-frame facts of the physical-mode Monte-Carlo runs (ldpc_phys_mc_run,
+ * _ex, _q), collected on the device next to the seven counters, which do not
+ * change.  While enabled, every such run on d clears the statistics at its
+ * start and fills them; they stay readable until the next run, a disable or
+ * the decoder's destruction.  Per SNR point p (the index into sigmas) of a run
+ * with max_iter = T over the frames frame0 .. frame0 + frames_per_point - 1:
+ *   hist[t], t < T   frames with conv == t;  hist[T]  frames with status != 0
+ *                    (sum = c[0], hist[T] = c[1], sum_{t<T} hist[t] = c[4],
+ *                    sum_{t<T} t hist[t] = c[3] of the run's counters row c);
+ *   undetected       {frames, info-bit errors} of the frames that converged
+ *                    (status 0) to info bits other than the ones sent -- the
+ *                    counters take such a frame for a success, as main.py does;
+ *   failed           records {global frame index, info-bit errors} of the frames
+ *                    with status != 0, at most max_failed per point, sorted by
+ *                    index.  With F failures: F <= max_failed -> all of them
+ *                    (their errors sum to c[2]); else max_failed distinct true
+ *                    failures, unspecified which, and dropped = F - max_failed.
+ *                    The index regenerates the frame: ldpc_generate_frames(seed,
+ *                    p, sigma_p, index, 1).
+ * ldpc_mc_stats_read: hist_len must be T + 1 of the last run; undetected_out
+ * [2]; failed_out [failed_cap][2] (may be NULL with failed_cap 0; failed_cap
+ * must hold the stored records); n_failed_out [2] = {stored, dropped}.  It
+ * synchronises the device.  LDPC_EINVAL when statistics are not enabled, no
+ * physical run has filled them, the last run was the parity-mode ldpc_mc_run
+ * (it collects none), point is out of range, hist_len is wrong or failed_cap is
+ * too small.  max_failed >= 0; 0 keeps no failed-frame list. */
+int ldpc_mc_stats_enable(ldpc_decoder *d, int32_t enable, int32_t max_failed);
+int ldpc_mc_stats_read(ldpc_decoder *d, int32_t point, int64_t *hist_out, int32_t hist_len,
+                       int64_t *undetected_out, int64_t *failed_out, int32_t failed_cap, int64_t *n_failed_out);
 
 /* ------------------------------------------------ multi-GPU (RCCL, xGMI)
  * One process per GPU; frames are sharded by global index, so the only

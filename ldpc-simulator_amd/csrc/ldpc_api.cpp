@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "ldpc_internal.h"
+#include "mc_stats_host.h"
 #include "spa_device.h"
 
 using ldpc::DevGraph;
@@ -107,6 +108,16 @@ struct ldpc_decoder {
     void *ord_tmp = nullptr;
     size_t ord_tmp_bytes = 0;
     DevState st{};
+    // Monte-Carlo statistics (ldpc_mc_stats_*): per point a header and hist[ms_T + 1], then the points'
+    // failed-frame records (mc_stats_host.h); ms_slots [cap] the tile paths' frame index of each slot
+    bool ms_on = false;
+    int ms_max_failed = 0;
+    unsigned long long *ms_buf = nullptr;
+    size_t ms_words = 0;
+    long long *ms_slots = nullptr;
+    int *ms_tile = nullptr;             // tile paths: slot_err [cap], then tile_arrive [cap_tiles] (McStats)
+    int ms_state = 0;  // 0: nothing to read, 1: the last physical run's statistics, 2: the last run was ldpc_mc_run
+    int ms_points = 0, ms_T = 0, ms_run_failed = 0;  // of the run in ms_buf
     // profiling (ldpc_profile_*)
     bool prof = false;
     struct Span {
@@ -792,6 +803,9 @@ int ldpc_decoder_destroy(ldpc_decoder *d) {
     (void)hipFree(d->pzb);
     (void)hipFree(d->pbits);
     (void)hipFree(d->pactive);
+    (void)hipFree(d->ms_buf);
+    (void)hipFree(d->ms_slots);
+    (void)hipFree(d->ms_tile);
     for (auto &sp : d->spans) {
         (void)hipEventDestroy(sp.a);
         (void)hipEventDestroy(sp.b);
@@ -1211,6 +1225,7 @@ int ldpc_mc_run(ldpc_decoder *d, uint64_t seed, int32_t n_points, const double *
     for (int p = 0; p < n_points; ++p)
         if (!(sigmas[p] > 0.0)) return ldpc_fail(LDPC_EINVAL, "ldpc_mc_run: sigma[%d] <= 0", p);
     DeviceGuard dg(d->g->device);
+    if (d->ms_on) d->ms_state = 2;  // parity mode collects no statistics
     if (int rc0 = ensure_messages(d)) return rc0;
     hipStream_t s = (hipStream_t)stream;
     const bool nllr = flags & LDPC_F_NLLR;
@@ -1459,13 +1474,58 @@ bool phys_compact_enabled() {
     return !e || atoi(e) != 0;
 }
 
+// Monte-Carlo statistics: start of a physical run.  Clears what the last run
+// left and, when enabled, sizes and zeroes the device arrays for this one.
+int mc_stats_begin(ldpc_decoder *d, int n_points, int max_iter, bool tiles, hipStream_t s) {
+    d->ms_state = 0;
+    if (!d->ms_on) return LDPC_OK;
+    const size_t words = ldpc::mc_stats_words(n_points, max_iter, d->ms_max_failed);
+    if (d->ms_words < words) {
+        (void)hipFree(d->ms_buf);
+        d->ms_buf = nullptr;
+        d->ms_words = 0;
+        if (int rc = dev_alloc(&d->ms_buf, words)) return rc;
+        d->ms_words = words;
+    }
+    const size_t cap = (size_t)d->cap_tiles * kTile;
+    if (tiles && !d->ms_slots)
+        if (int rc = dev_alloc(&d->ms_slots, cap)) return rc;
+    if (tiles && !d->ms_tile)
+        if (int rc = dev_alloc(&d->ms_tile, cap + (size_t)d->cap_tiles)) return rc;
+    if (tiles) HIP_TRY(hipMemsetAsync(d->ms_tile, 0, sizeof(int) * (cap + (size_t)d->cap_tiles), s));
+    HIP_TRY(hipMemsetAsync(d->ms_buf, 0, sizeof(unsigned long long) * words, s));
+    d->ms_points = n_points;
+    d->ms_T = max_iter;
+    d->ms_run_failed = d->ms_max_failed;
+    return LDPC_OK;
+}
+
+// The kernels' view of point p of the run mc_stats_begin prepared (off: all null).
+void mc_stats_point(const ldpc_decoder *d, int p, int64_t frame_base, ldpc::McStats *out) {
+    ldpc::McStats &ms = *out;
+    ms = ldpc::McStats{};
+    if (!d->ms_on) return;
+    const size_t pw = ldpc::mc_stats_point_words(d->ms_T);
+    unsigned long long *head = d->ms_buf + (size_t)p * pw;
+    ms.und = head;
+    ms.hist = head + ldpc::kMcStatsHead;
+    ms.failed = reinterpret_cast<long long *>(d->ms_buf + (size_t)d->ms_points * pw) +
+                (size_t)p * 2 * (size_t)d->ms_run_failed;
+    ms.slot_frame = d->ms_slots;
+    ms.slot_err = d->ms_tile;
+    ms.tile_arrive = d->ms_tile ? d->ms_tile + (size_t)d->cap_tiles * kTile : nullptr;
+    ms.frame_base = frame_base;
+    ms.max_failed = d->ms_run_failed;
+    ms.max_iter = d->ms_T;
+}
+
 // The layered schedule on the tiles (phys_tile.hip): per iteration one launch
 // per layer, in order on the stream, then the syndrome of b = (L < 0) and the
 // exits -- on the device every iteration, so the results never depend on the
 // polls.  The host polls and compacts as phys_tile_decode does; the exit of
 // iteration max_iter - 1 stops the frames still running (no final sweep).
 int phys_tile_decode_layered(ldpc_decoder *d, const DevGraph &P, int max_iter, bool from_ch, hipStream_t s,
-                             unsigned long long *ctr, const PhysRule &rule) {
+                             unsigned long long *ctr, const PhysRule &rule, const ldpc::McStats &ms) {
     if (int rc = ensure_pactive(d, max_iter)) return rc;
     DevState st = d->st;  // st.ntiles shrinks with each compaction
     const PhysTile pt = phys_tile(d);
@@ -1492,8 +1552,8 @@ int phys_tile_decode_layered(ldpc_decoder *d, const DevGraph &P, int max_iter, b
             const int nt = (running[1] + kTile - 1) / kTile;
             if (ctr && compact && nt < st.ntiles && 4 * (int64_t)running[1] <= (int64_t)st.ntiles * kTile) {
                 if (!d->cpairs && dev_alloc(&d->cpairs, 1 + 2 * (size_t)cap)) return LDPC_ENOMEM;
-                HIP_TRY(timed(d, LDPC_K_COUNT, s, [&] { return ldpc::launch_phys_tile_count(P, st, pt, ctr, s); }));
-                HIP_TRY(ldpc::launch_phys_compact(P, st, pt, nt, cap, d->cpairs, s));
+                HIP_TRY(timed(d, LDPC_K_COUNT, s, [&] { return ldpc::launch_phys_tile_count(P, st, pt, ctr, s, ms); }));
+                HIP_TRY(ldpc::launch_phys_compact(P, st, pt, nt, cap, d->cpairs, s, ms.hist ? ms.slot_frame : nullptr));
                 st.ntiles = nt;
             }
         }
@@ -1510,8 +1570,9 @@ int phys_tile_decode_layered(ldpc_decoder *d, const DevGraph &P, int max_iter, b
 // most a quarter of the launched slots hold them, the finished frames counted
 // into ctr first (phys_tile.hip).
 int phys_tile_decode(ldpc_decoder *d, const DevGraph &P, int max_iter, bool from_ch, hipStream_t s,
-                     unsigned long long *ctr = nullptr, const PhysRule &rule = PhysRule{}) {
-    if (rule.layer_ptr) return phys_tile_decode_layered(d, P, max_iter, from_ch, s, ctr, rule);
+                     unsigned long long *ctr = nullptr, const PhysRule &rule = PhysRule{},
+                     const ldpc::McStats &ms = ldpc::McStats{}) {
+    if (rule.layer_ptr) return phys_tile_decode_layered(d, P, max_iter, from_ch, s, ctr, rule, ms);
     if (int rc = ensure_pactive(d, max_iter)) return rc;
     DevState st = d->st;  // st.ntiles shrinks with each compaction
     const PhysTile pt = phys_tile(d);
@@ -1544,8 +1605,8 @@ int phys_tile_decode(ldpc_decoder *d, const DevGraph &P, int max_iter, bool from
             // (a quarter: half measured the same, profiles/r5_ab/r5am_ab)
             if (ctr && compact && nt < st.ntiles && 4 * (int64_t)running[1] <= (int64_t)st.ntiles * kTile) {
                 if (!d->cpairs && dev_alloc(&d->cpairs, 1 + 2 * (size_t)cap)) return LDPC_ENOMEM;
-                HIP_TRY(timed(d, LDPC_K_COUNT, s, [&] { return ldpc::launch_phys_tile_count(P, st, pt, ctr, s); }));
-                HIP_TRY(ldpc::launch_phys_compact(P, st, pt, nt, cap, d->cpairs, s));
+                HIP_TRY(timed(d, LDPC_K_COUNT, s, [&] { return ldpc::launch_phys_tile_count(P, st, pt, ctr, s, ms); }));
+                HIP_TRY(ldpc::launch_phys_compact(P, st, pt, nt, cap, d->cpairs, s, ms.hist ? ms.slot_frame : nullptr));
                 st.ntiles = nt;
             }
         }
@@ -1656,6 +1717,7 @@ int phys_mc_any(const char *fn, ldpc_decoder *d, const ldpc_graph *gp, uint64_t 
         d->counters_cap = need;
     }
     HIP_TRY(hipMemsetAsync(d->counters, 0, sizeof(unsigned long long) * need, s));
+    if (int rc = mc_stats_begin(d, n_points, max_iter, !lds, s)) return rc;
     const int64_t cap = (int64_t)d->cap_tiles * kTile;
     for (int p = 0; p < n_points; ++p) {
         unsigned long long *ctr = d->counters + (size_t)p * LDPC_MC_NCOUNT;
@@ -1663,6 +1725,8 @@ int phys_mc_any(const char *fn, ldpc_decoder *d, const ldpc_graph *gp, uint64_t 
             const int cnt = (int)std::min<int64_t>(cap, frames_per_point - start);
             state_bind(d, (cnt + kTile - 1) / kTile, cnt);
             const DevState st = d->st;
+            ldpc::McStats ms;
+            mc_stats_point(d, p, frame0 + start, &ms);
             // frames go straight to the decoder's fp32 Lambda: tile layout for the
             // HBM tile decoder, row-major (contiguous per frame) for the LDS decoder
             float *rows = (float *)d->llr_stage;  // cap x n doubles: room for cap x n floats
@@ -1675,14 +1739,15 @@ int phys_mc_any(const char *fn, ldpc_decoder *d, const ldpc_graph *gp, uint64_t 
                     if (rule.layer_ptr)
                         return ldpc::launch_phys_layered(P, nullptr, rows, 2, cnt, max_iter, nullptr, nullptr, nullptr,
                                                          nullptr, nullptr, st.ubits, ctr,
-                                                         std::min(phys_layered_grid(P, rule), cnt), s, rule);
+                                                         std::min(phys_layered_grid(P, rule), cnt), s, rule, ms);
                     return ldpc::launch_phys(P, nullptr, rows, 2, cnt, max_iter, nullptr, nullptr, nullptr, nullptr,
-                                             nullptr, st.ubits, ctr, std::min(phys_grid(P), cnt), s, rule);
+                                             nullptr, st.ubits, ctr, std::min(phys_grid(P), cnt), s, rule, ms);
                 }));
             } else {
-                if (int rc = phys_tile_decode(d, P, max_iter, false, s, ctr, rule)) return rc;
+                if (ms.hist) HIP_TRY(ldpc::launch_mc_stats_slots(ms.slot_frame, ms.frame_base, cnt, s));
+                if (int rc = phys_tile_decode(d, P, max_iter, false, s, ctr, rule, ms)) return rc;
                 HIP_TRY(timed(d, LDPC_K_COUNT, s,
-                              [&] { return ldpc::launch_phys_tile_count(P, st, phys_tile(d), ctr, s); }));
+                              [&] { return ldpc::launch_phys_tile_count(P, st, phys_tile(d), ctr, s, ms); }));
             }
         }
     }
@@ -1690,6 +1755,7 @@ int phys_mc_any(const char *fn, ldpc_decoder *d, const ldpc_graph *gp, uint64_t 
     HIP_TRY(hipMemcpyAsync(h.data(), d->counters, sizeof(unsigned long long) * need, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     for (int i = 0; i < need; ++i) counters_out[i] = (int64_t)h[i];
+    if (d->ms_on) d->ms_state = 1;
     return LDPC_OK;
 }
 
@@ -1880,7 +1946,8 @@ ldpc::QTile quant_tile(ldpc_decoder *d, const ldpc::QuantRule &rule) {
 // phys_tile_decode_layered's; the exits run on the device every iteration, so
 // no result depends on a poll.
 int phys_qtile_decode(ldpc_decoder *d, const DevGraph &P, int max_iter, const float *lam32, hipStream_t s,
-                      unsigned long long *ctr, const ldpc::QuantRule &rule) {
+                      unsigned long long *ctr, const ldpc::QuantRule &rule,
+                      const ldpc::McStats &ms = ldpc::McStats{}) {
     if (int rc = ensure_pactive(d, max_iter)) return rc;
     DevState st = d->st;  // st.ntiles shrinks with each compaction
     const ldpc::QTile qt = quant_tile(d, rule);
@@ -1922,8 +1989,10 @@ int phys_qtile_decode(ldpc_decoder *d, const DevGraph &P, int max_iter, const fl
             const int nt = (running[1] + kTile - 1) / kTile;
             if (ctr && compact && nt < st.ntiles && 4 * (int64_t)running[1] <= (int64_t)st.ntiles * kTile) {
                 if (!d->cpairs && dev_alloc(&d->cpairs, 1 + 2 * (size_t)cap)) return LDPC_ENOMEM;
-                HIP_TRY(timed(d, LDPC_K_COUNT, s, [&] { return ldpc::launch_phys_qtile_count(P, st, qt, ctr, s); }));
-                HIP_TRY(ldpc::launch_phys_qtile_compact(P, st, qt, !layered, nt, cap, d->cpairs, s));
+                HIP_TRY(timed(d, LDPC_K_COUNT, s,
+                              [&] { return ldpc::launch_phys_qtile_count(P, st, qt, ctr, s, ms); }));
+                HIP_TRY(ldpc::launch_phys_qtile_compact(P, st, qt, !layered, nt, cap, d->cpairs, s,
+                                                        ms.hist ? ms.slot_frame : nullptr));
                 st.ntiles = nt;
             }
         }
@@ -2085,6 +2154,7 @@ int ldpc_phys_mc_run_q(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int
         d->counters_cap = need;
     }
     HIP_TRY(hipMemsetAsync(d->counters, 0, sizeof(unsigned long long) * need, s));
+    if (int rc = mc_stats_begin(d, n_points, max_iter, rule.tile, s)) return rc;
     const int64_t cap = (int64_t)d->cap_tiles * kTile;
     for (int p = 0; p < n_points; ++p) {
         unsigned long long *ctr = d->counters + (size_t)p * LDPC_MC_NCOUNT;
@@ -2092,6 +2162,8 @@ int ldpc_phys_mc_run_q(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int
             const int cnt = (int)std::min<int64_t>(cap, frames_per_point - start);
             state_bind(d, (cnt + kTile - 1) / kTile, cnt);
             const DevState st = d->st;
+            ldpc::McStats ms;
+            mc_stats_point(d, p, frame0 + start, &ms);
             // frames as fp32 Lambda: tiles (pLam) for the HBM tile decoder, rows for the LDS decoder
             float *rows = (float *)d->llr_stage;
             HIP_TRY(timed(d, LDPC_K_GEN, s, [&] {
@@ -2099,14 +2171,16 @@ int ldpc_phys_mc_run_q(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int
                                            rule.tile ? ldpc::kFramesTileLambda : ldpc::kFramesRowLambda, rows, s);
             }));
             if (rule.tile) {
-                if (int rc = phys_qtile_decode(d, P, max_iter, d->pLam, s, ctr, rule)) return rc;
-                HIP_TRY(timed(d, LDPC_K_COUNT, s,
-                              [&] { return ldpc::launch_phys_qtile_count(P, st, quant_tile(d, rule), ctr, s); }));
+                if (ms.hist) HIP_TRY(ldpc::launch_mc_stats_slots(ms.slot_frame, ms.frame_base, cnt, s));
+                if (int rc = phys_qtile_decode(d, P, max_iter, d->pLam, s, ctr, rule, ms)) return rc;
+                HIP_TRY(timed(d, LDPC_K_COUNT, s, [&] {
+                    return ldpc::launch_phys_qtile_count(P, st, quant_tile(d, rule), ctr, s, ms);
+                }));
                 continue;
             }
             HIP_TRY(timed(d, LDPC_K_PHYS, s, [&] {
                 return ldpc::launch_phys_quant(P, nullptr, rows, cnt, max_iter, nullptr, nullptr, nullptr, nullptr,
-                                               nullptr, st.ubits, ctr, phys_quant_max_grid(), s, rule);
+                                               nullptr, st.ubits, ctr, phys_quant_max_grid(), s, rule, ms);
             }));
         }
     }
@@ -2114,6 +2188,57 @@ int ldpc_phys_mc_run_q(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int
     HIP_TRY(hipMemcpyAsync(h.data(), d->counters, sizeof(unsigned long long) * need, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     for (int i = 0; i < need; ++i) counters_out[i] = (int64_t)h[i];
+    if (d->ms_on) d->ms_state = 1;
+    return LDPC_OK;
+}
+
+// ------------------------------------------------- Monte-Carlo statistics
+int ldpc_mc_stats_enable(ldpc_decoder *d, int32_t enable, int32_t max_failed) {
+    if (max_failed < 0) return ldpc_fail(LDPC_EINVAL, "ldpc_mc_stats_enable: max_failed %d < 0", max_failed);
+    if (!d) return ldpc_fail(LDPC_EINVAL, "ldpc_mc_stats_enable: NULL decoder");
+    d->ms_on = enable != 0;
+    d->ms_max_failed = d->ms_on ? max_failed : 0;
+    d->ms_state = 0;  // what an earlier run left is gone
+    return LDPC_OK;
+}
+
+int ldpc_mc_stats_read(ldpc_decoder *d, int32_t point, int64_t *hist_out, int32_t hist_len, int64_t *undetected_out,
+                       int64_t *failed_out, int32_t failed_cap, int64_t *n_failed_out) {
+    const char *fn = "ldpc_mc_stats_read";
+    if (!d) return ldpc_fail(LDPC_EINVAL, "%s: NULL decoder", fn);
+    if (!hist_out || !undetected_out || !n_failed_out || failed_cap < 0 || (failed_cap > 0 && !failed_out))
+        return ldpc_fail(LDPC_EINVAL, "%s: bad arguments", fn);
+    if (!d->ms_on) return ldpc_fail(LDPC_EINVAL, "%s: statistics are not enabled (ldpc_mc_stats_enable)", fn);
+    if (d->ms_state == 2)
+        return ldpc_fail(LDPC_EINVAL, "%s: the last run was ldpc_mc_run, which collects no statistics", fn);
+    if (d->ms_state != 1)
+        return ldpc_fail(LDPC_EINVAL, "%s: no physical-mode Monte-Carlo run since statistics were enabled", fn);
+    if (point < 0 || point >= d->ms_points)
+        return ldpc_fail(LDPC_EINVAL, "%s: point %d out of range (the run had %d)", fn, point, d->ms_points);
+    if (hist_len != d->ms_T + 1)
+        return ldpc_fail(LDPC_EINVAL, "%s: hist_len %d != max_iter + 1 = %d of the last run", fn, hist_len,
+                         d->ms_T + 1);
+    DeviceGuard dg(d->g->device);
+    const size_t pw = ldpc::mc_stats_point_words(d->ms_T);
+    std::vector<unsigned long long> head(pw);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(head.data(), d->ms_buf + (size_t)point * pw, sizeof(unsigned long long) * pw,
+                      hipMemcpyDeviceToHost));
+    const int64_t stored = ldpc::mc_stats_stored(head[2], d->ms_run_failed);
+    if (failed_cap < stored)
+        return ldpc_fail(LDPC_EINVAL, "%s: failed_cap %d < %lld stored records", fn, failed_cap, (long long)stored);
+    if (stored > 0) {
+        std::vector<int64_t> rec(2 * (size_t)stored);
+        const unsigned long long *src =
+            d->ms_buf + (size_t)d->ms_points * pw + (size_t)point * 2 * (size_t)d->ms_run_failed;
+        HIP_TRY(hipMemcpy(rec.data(), src, sizeof(int64_t) * rec.size(), hipMemcpyDeviceToHost));
+        ldpc::mc_stats_sort_records(rec.data(), stored, failed_out);
+    }
+    undetected_out[0] = (int64_t)head[0];
+    undetected_out[1] = (int64_t)head[1];
+    for (int t = 0; t <= d->ms_T; ++t) hist_out[t] = (int64_t)head[ldpc::kMcStatsHead + t];
+    n_failed_out[0] = stored;
+    n_failed_out[1] = (int64_t)head[2] - stored;
     return LDPC_OK;
 }
 

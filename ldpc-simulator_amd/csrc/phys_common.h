@@ -65,9 +65,57 @@ struct FrameCounts {
     }
 };
 
+// Monte-Carlo statistics (McStats) of the frames one workgroup decodes.  At a
+// clean channel every frame lands in the first bins, so thread 0 keeps those,
+// and the failed frames' bin, in a small static LDS array (registers would
+// cost the decoders occupancy; dynamic LDS a frame per CU) and adds them to the
+// point's histogram once, as FrameCounts::flush does.  Later bins, undetected
+// errors and failure records are rare per unit of work: one atomic each.
+constexpr int kMcHotBins = 4;
+constexpr int kMcBins = kMcHotBins + 1;  // s_bins: bins 0 .. kMcHotBins - 1, then the failed frames
+
+__device__ __forceinline__ void mc_stats_begin(unsigned *s_bins, int tid) {
+    if (tid != 0) return;
+#pragma unroll
+    for (int i = 0; i < kMcBins; ++i) s_bins[i] = 0u;
+}
+
+// thread 0, once per frame: err = the frame's info-bit errors
+__device__ __forceinline__ void mc_stats_frame(const McStats &ms, long long frame, int conv, int err,
+                                               unsigned *s_bins) {
+    if (conv < 0) {
+        ++s_bins[kMcHotBins];
+        const unsigned long long i = atomicAdd(&ms.und[2], 1ull);
+        if (i < (unsigned long long)ms.max_failed) {
+            ms.failed[2 * i] = frame;
+            ms.failed[2 * i + 1] = err;
+        }
+        return;
+    }
+    if (conv < kMcHotBins) ++s_bins[conv];
+    else atomicAdd(&ms.hist[min(conv, ms.max_iter - 1)], 1ull);
+    if (err) {  // converged to another codeword
+        atomicAdd(&ms.und[0], 1ull);
+        atomicAdd(&ms.und[1], (unsigned long long)err);
+    }
+}
+
+__device__ __forceinline__ void mc_stats_flush(const McStats &ms, const unsigned *s_bins, int tid) {
+    if (tid != 0) return;
+#pragma unroll
+    for (int i = 0; i < kMcHotBins; ++i)
+        if (s_bins[i] && i < ms.max_iter) atomicAdd(&ms.hist[i], (unsigned long long)s_bins[i]);
+    if (s_bins[kMcHotBins]) atomicAdd(&ms.hist[ms.max_iter], (unsigned long long)s_bins[kMcHotBins]);
+}
+
 // Outputs and Monte-Carlo counters of frame f (conv = -1: not converged).
-__device__ __forceinline__ void frame_finish(const PhysArgs &a, int f, int conv, const float *L, int *s_err,
-                                             int tid, int nt, FrameCounts &fc) {
+// STATS: the kernel's statistics instantiation (the host launches it when the
+// point's McStats is set: ms, and s_bins, the workgroup's kMcBins bins of
+// mc_stats_begin / _flush); the other one is the code without statistics,
+// nothing added (ms unused, s_bins null).
+template <bool STATS>
+__device__ __forceinline__ void frame_finish(const PhysArgs &a, const McStats &ms, int f, int conv, const float *L,
+                                             int *s_err, unsigned *s_bins, int tid, int nt, FrameCounts &fc) {
     const DevGraph &g = a.g;
     const int iters = conv >= 0 ? conv + 1 : a.max_iter;
     for (int j = tid; j < g.n; j += nt) {
@@ -83,7 +131,10 @@ __device__ __forceinline__ void frame_finish(const PhysArgs &a, int f, int conv,
     }
     if (a.ctr) {
         __syncthreads();
-        if (conv < 0) {  // BER counts failed frames only (main.py:130-138)
+        // BER counts failed frames only (main.py:130-138); the statistics look
+        // at the converged ones too (undetected errors)
+        constexpr bool stats = STATS;
+        if (conv < 0 || stats) {
             const int kw = (g.k + 31) >> 5;
             int my = 0;
             for (int j = tid; j < g.k; j += nt) {
@@ -103,6 +154,7 @@ __device__ __forceinline__ void frame_finish(const PhysArgs &a, int f, int conv,
                 fc.v[4] += 1ull;
             }
             fc.v[6] += (unsigned long long)iters;
+            if constexpr (stats) mc_stats_frame(ms, ms.frame_base + f, conv, *s_err, s_bins);
         }
     }
     __syncthreads();  // LDS reused by the next frame

@@ -37,16 +37,22 @@ namespace {
 
 // CN: the check rule (kCnSpa: phi domain, above; kCnNms / kCnOms: min-sum,
 // first sweep for the two smallest |M| and the sign parity, second to write).
-template <int CN>
-__global__ __launch_bounds__(256) void phys_kernel(PhysArgs a) {
+template <int CN, bool STATS>
+__global__ __launch_bounds__(256) void phys_kernel(PhysArgs a, McStats ms) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const DevGraph &g = a.g;
     float *E = lds;                 // [nnz]
     float *L = E + ((g.nnz + 3) & ~3);  // [n]
     float *Lam = L + ((g.n + 3) & ~3);  // [n]
     __shared__ int s_err;
+    unsigned *s_bins = nullptr;
+    if constexpr (STATS) {  // static LDS of the statistics instantiation only
+        __shared__ unsigned bins[kMcBins];
+        s_bins = bins;
+    }
     FrameCounts fc;
     const int tid = threadIdx.x, nt = blockDim.x;
+    if constexpr (STATS) mc_stats_begin(s_bins, tid);
     for (int f = blockIdx.x; f < a.count; f += gridDim.x) {
         frame_load(a, f, E, L, Lam, tid, nt);
         __syncthreads();
@@ -103,9 +109,10 @@ __global__ __launch_bounds__(256) void phys_kernel(PhysArgs a) {
                 break;
             }
         }
-        frame_finish(a, f, conv, L, &s_err, tid, nt, fc);
+        frame_finish<STATS>(a, ms, f, conv, L, &s_err, s_bins, tid, nt, fc);
     }
     if (tid == 0) fc.flush(a.ctr);
+    if constexpr (STATS) mc_stats_flush(ms, s_bins, tid);
 }
 
 // The same decoder with every thread's rows and columns fixed for the whole
@@ -114,16 +121,22 @@ __global__ __launch_bounds__(256) void phys_kernel(PhysArgs a) {
 // frame: no index loads in the iteration loop), and phi(|M|) kept in registers
 // between the two sweeps of a row (phys_cn_tile does the same).  Identical
 // operations in identical order as phys_kernel: bit-identical results.
-template <int CN, int NT, int RPT, int RDEG, int CPT, int CDEG, int WPS>
-__global__ __launch_bounds__(NT, WPS) void phys_reg_kernel(PhysArgs a) {
+template <int CN, int NT, int RPT, int RDEG, int CPT, int CDEG, int WPS, bool STATS>
+__global__ __launch_bounds__(NT, WPS) void phys_reg_kernel(PhysArgs a, McStats ms) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const DevGraph &g = a.g;
     float *E = lds;
     float *L = E + ((g.nnz + 3) & ~3);
     float *Lam = L + ((g.n + 3) & ~3);
     __shared__ int s_err;
+    unsigned *s_bins = nullptr;
+    if constexpr (STATS) {  // static LDS of the statistics instantiation only
+        __shared__ unsigned bins[kMcBins];
+        s_bins = bins;
+    }
     FrameCounts fc;
     const int tid = threadIdx.x;
+    if constexpr (STATS) mc_stats_begin(s_bins, tid);
     int rbeg[RPT], rdeg[RPT];
     uint32_t rc[RPT][RDEG / 2];
 #pragma unroll
@@ -237,9 +250,10 @@ __global__ __launch_bounds__(NT, WPS) void phys_reg_kernel(PhysArgs a) {
                 break;
             }
         }
-        frame_finish(a, f, conv, L, &s_err, tid, NT, fc);
+        frame_finish<STATS>(a, ms, f, conv, L, &s_err, s_bins, tid, NT, fc);
     }
     if (tid == 0) fc.flush(a.ctr);
+    if constexpr (STATS) mc_stats_flush(ms, s_bins, tid);
 }
 
 }  // namespace
@@ -282,26 +296,26 @@ int phys_block_threads(const DevGraph &g) { return reg_shape(g) >= 0 ? kRegNT : 
 
 namespace {
 
-template <int CN>
-void launch_phys_rule(const PhysArgs &a, int grid, size_t lds, int wps, hipStream_t s) {
+template <int CN, bool STATS>
+void launch_phys_rule(const PhysArgs &a, const McStats &ms, int grid, size_t lds, int wps, hipStream_t s) {
     // the 4-wave A/B variants exist for the SPA rule only
     const bool w6 = wps == 6 || CN != kCnSpa;
     switch (reg_shape(a.g)) {
-    case 0: phys_reg_kernel<CN, kRegNT, 1, 8, 1, 8, 6><<<grid, kRegNT, lds, s>>>(a); break;
-    case 1: phys_reg_kernel<CN, kRegNT, 1, 8, 2, 8, 6><<<grid, kRegNT, lds, s>>>(a); break;
+    case 0: phys_reg_kernel<CN, kRegNT, 1, 8, 1, 8, 6, STATS><<<grid, kRegNT, lds, s>>>(a, ms); break;
+    case 1: phys_reg_kernel<CN, kRegNT, 1, 8, 2, 8, 6, STATS><<<grid, kRegNT, lds, s>>>(a, ms); break;
     case 2:
-        if (w6) phys_reg_kernel<CN, kRegNT, 2, 8, 3, 8, 6><<<grid, kRegNT, lds, s>>>(a);
-        else if constexpr (CN == kCnSpa) phys_reg_kernel<CN, kRegNT, 2, 8, 3, 8, 4><<<grid, kRegNT, lds, s>>>(a);
+        if (w6) phys_reg_kernel<CN, kRegNT, 2, 8, 3, 8, 6, STATS><<<grid, kRegNT, lds, s>>>(a, ms);
+        else if constexpr (CN == kCnSpa) phys_reg_kernel<CN, kRegNT, 2, 8, 3, 8, 4, STATS><<<grid, kRegNT, lds, s>>>(a, ms);
         break;
     case 3:
-        if (w6) phys_reg_kernel<CN, kRegNT, 2, 16, 5, 8, 6><<<grid, kRegNT, lds, s>>>(a);
-        else if constexpr (CN == kCnSpa) phys_reg_kernel<CN, kRegNT, 2, 16, 5, 8, 4><<<grid, kRegNT, lds, s>>>(a);
+        if (w6) phys_reg_kernel<CN, kRegNT, 2, 16, 5, 8, 6, STATS><<<grid, kRegNT, lds, s>>>(a, ms);
+        else if constexpr (CN == kCnSpa) phys_reg_kernel<CN, kRegNT, 2, 16, 5, 8, 4, STATS><<<grid, kRegNT, lds, s>>>(a, ms);
         break;
     case 4:
-        if (w6) phys_reg_kernel<CN, kRegNT, 3, 8, 5, 8, 6><<<grid, kRegNT, lds, s>>>(a);
-        else if constexpr (CN == kCnSpa) phys_reg_kernel<CN, kRegNT, 3, 8, 5, 8, 4><<<grid, kRegNT, lds, s>>>(a);
+        if (w6) phys_reg_kernel<CN, kRegNT, 3, 8, 5, 8, 6, STATS><<<grid, kRegNT, lds, s>>>(a, ms);
+        else if constexpr (CN == kCnSpa) phys_reg_kernel<CN, kRegNT, 3, 8, 5, 8, 4, STATS><<<grid, kRegNT, lds, s>>>(a, ms);
         break;
-    default: phys_kernel<CN><<<grid, 256, lds, s>>>(a);
+    default: phys_kernel<CN, STATS><<<grid, 256, lds, s>>>(a, ms);
     }
 }
 
@@ -309,9 +323,10 @@ void launch_phys_rule(const PhysArgs &a, int grid, size_t lds, int wps, hipStrea
 
 hipError_t launch_phys(const DevGraph &g, const double *llr, const float *lam, int layout, int count, int max_iter,
                        uint8_t *z, int *conv, int *status, int *iters, float *post, const uint32_t *ubits,
-                       unsigned long long *ctr, int grid, hipStream_t s, const PhysRule &rule) {
+                       unsigned long long *ctr, int grid, hipStream_t s, const PhysRule &rule, const McStats &ms_in) {
     PhysArgs a{g, llr, lam, layout, count, max_iter, z, conv, status, iters, post, ubits, ctr, rule.param,
                nullptr, nullptr, 0};
+    const McStats ms = ctr ? ms_in : McStats{};  // ms.hist set: the kernels' statistics instantiations
     const size_t lds = phys_lds_bytes(g);
     if (count <= 0) return hipSuccess;
     // min waves per SIMD of the large shapes: 6 = three 8-wave frames per CU (the
@@ -322,9 +337,18 @@ hipError_t launch_phys(const DevGraph &g, const double *llr, const float *lam, i
         return e ? atoi(e) : 6;
     }();
     switch (rule.cn) {
-    case kCnSpa: launch_phys_rule<kCnSpa>(a, grid, lds, wps, s); break;
-    case kCnNms: launch_phys_rule<kCnNms>(a, grid, lds, wps, s); break;
-    case kCnOms: launch_phys_rule<kCnOms>(a, grid, lds, wps, s); break;
+    case kCnSpa:
+        if (ms.hist) launch_phys_rule<kCnSpa, true>(a, ms, grid, lds, wps, s);
+        else launch_phys_rule<kCnSpa, false>(a, ms, grid, lds, wps, s);
+        break;
+    case kCnNms:
+        if (ms.hist) launch_phys_rule<kCnNms, true>(a, ms, grid, lds, wps, s);
+        else launch_phys_rule<kCnNms, false>(a, ms, grid, lds, wps, s);
+        break;
+    case kCnOms:
+        if (ms.hist) launch_phys_rule<kCnOms, true>(a, ms, grid, lds, wps, s);
+        else launch_phys_rule<kCnOms, false>(a, ms, grid, lds, wps, s);
+        break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

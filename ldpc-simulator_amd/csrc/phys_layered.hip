@@ -31,15 +31,21 @@
 namespace ldpc {
 namespace {
 
-template <int CN>
-__global__ __launch_bounds__(256) void phys_layered_kernel(PhysArgs a) {
+template <int CN, bool STATS>
+__global__ __launch_bounds__(256) void phys_layered_kernel(PhysArgs a, McStats ms) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const DevGraph &g = a.g;
     float *E = lds;                     // [nnz]
     float *L = E + ((g.nnz + 3) & ~3);  // [n]
     __shared__ int s_err;
+    unsigned *s_bins = nullptr;
+    if constexpr (STATS) {  // static LDS of the statistics instantiation only
+        __shared__ unsigned bins[kMcBins];
+        s_bins = bins;
+    }
     FrameCounts fc;
     const int tid = threadIdx.x, nt = blockDim.x;
+    if constexpr (STATS) mc_stats_begin(s_bins, tid);
     for (int f = blockIdx.x; f < a.count; f += gridDim.x) {
         for (int j = tid; j < g.n; j += nt) L[j] = frame_lambda(a, f, j);
         for (int e = tid; e < g.nnz; e += nt) E[e] = 0.0f;
@@ -83,9 +89,10 @@ __global__ __launch_bounds__(256) void phys_layered_kernel(PhysArgs a) {
                 break;
             }
         }
-        frame_finish(a, f, conv, L, &s_err, tid, nt, fc);
+        frame_finish<STATS>(a, ms, f, conv, L, &s_err, s_bins, tid, nt, fc);
     }
     if (tid == 0) fc.flush(a.ctr);
+    if constexpr (STATS) mc_stats_flush(ms, s_bins, tid);
 }
 
 }  // namespace
@@ -106,16 +113,23 @@ int phys_layered_threads(const PhysRule &rule) {
 hipError_t launch_phys_layered(const DevGraph &g, const double *llr, const float *lam, int layout, int count,
                                int max_iter, uint8_t *z, int *conv, int *status, int *iters, float *post,
                                const uint32_t *ubits, unsigned long long *ctr, int grid, hipStream_t s,
-                               const PhysRule &rule) {
+                               const PhysRule &rule, const McStats &ms_in) {
     if (!rule.layer_ptr || !rule.layer_rows || rule.n_layers <= 0) return hipErrorInvalidValue;
     PhysArgs a{g, llr, lam, layout, count, max_iter, z, conv, status, iters, post, ubits, ctr, rule.param,
                rule.layer_ptr, rule.layer_rows, rule.n_layers};
+    const McStats ms = ctr ? ms_in : McStats{};  // ms.hist set: the kernel's statistics instantiation
     if (count <= 0) return hipSuccess;
     const size_t lds = phys_layered_lds_bytes(g);
     const int nt = phys_layered_threads(rule);
     switch (rule.cn) {
-    case kCnNms: phys_layered_kernel<kCnNms><<<grid, nt, lds, s>>>(a); break;
-    case kCnOms: phys_layered_kernel<kCnOms><<<grid, nt, lds, s>>>(a); break;
+    case kCnNms:
+        if (ms.hist) phys_layered_kernel<kCnNms, true><<<grid, nt, lds, s>>>(a, ms);
+        else phys_layered_kernel<kCnNms, false><<<grid, nt, lds, s>>>(a, ms);
+        break;
+    case kCnOms:
+        if (ms.hist) phys_layered_kernel<kCnOms, true><<<grid, nt, lds, s>>>(a, ms);
+        else phys_layered_kernel<kCnOms, false><<<grid, nt, lds, s>>>(a, ms);
+        break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -469,7 +469,7 @@ __global__ void phys_qtile_out_kernel(DevGraph g, DevState st, QTile qt, uint8_t
 
 // main.py counters; block = one wavefront x (tile, 1024 info columns) (phys_tile_count)
 __global__ __launch_bounds__(64) void phys_qtile_count_kernel(DevGraph g, DevState st, QTile qt,
-                                                              unsigned long long *ctr) {
+                                                              unsigned long long *ctr, McStats ms) {
     const int kw = (g.k + 31) >> 5;
     const int per_tile = (g.k + 1023) >> 10 > 0 ? (g.k + 1023) >> 10 : 1;
     const int tile = blockIdx.x / per_tile, part = blockIdx.x % per_tile;
@@ -478,7 +478,7 @@ __global__ __launch_bounds__(64) void phys_qtile_count_kernel(DevGraph g, DevSta
     const bool valid = st.done[f] == 1;  // finished and not counted yet
     const bool failed = valid && st.status[f] != 0;
     unsigned long long err = 0;
-    if (failed) {  // BER counts failed frames only
+    if (ms.hist ? valid : failed) {  // BER counts failed frames only; the statistics need the converged ones too
         const uint32_t *Ut = st.ubits + (size_t)tile * kw * kTile + lane;
         const int16_t *Lt = qt.L + (size_t)tile * g.n * kTile + lane;
         const int j1 = min(g.k, (part + 1) * 1024);
@@ -487,8 +487,9 @@ __global__ __launch_bounds__(64) void phys_qtile_count_kernel(DevGraph g, DevSta
             err += (u != (Lt[j * kTile] < 0 ? 1u : 0u)) ? 1 : 0;
         }
     }
-    const unsigned long long e = wave_sum(err);
+    const unsigned long long e = wave_sum(failed ? err : 0ull);
     if (lane == 0 && e) atomicAdd(&ctr[2], e);
+    if (ms.hist) mc_stats_tile(ms, st, tile, per_tile, lane, valid, failed, (int)err);
     if (part != 0) return;
     const int cv = valid ? st.conv[f] : -1;
     unsigned long long v[7] = {valid ? 1ull : 0ull, failed ? 1ull : 0ull, 0, cv >= 0 ? (unsigned long long)cv : 0,
@@ -538,10 +539,12 @@ __global__ void phys_qcompact_move_kernel(DevGraph g, DevState st, QTile qt, int
         st.ubits[(dT * kw + it) * kTile + dl] = st.ubits[(sT * kw + it) * kTile + sl];
     }
 }
-__global__ void phys_qcompact_flags_kernel(DevState st, QTile qt, int cap, const int *pairs) {
+__global__ void phys_qcompact_flags_kernel(DevState st, QTile qt, int cap, const int *pairs,
+                                           long long *slot_frame) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= pairs[0]) return;
     const int src = pairs[1 + p], dst = pairs[1 + cap + p];
+    if (slot_frame) slot_frame[dst] = slot_frame[src];  // the frame's global index moves with it
     st.done[dst] = 0;
     st.conv[dst] = -1;
     st.status[dst] = 1;
@@ -671,19 +674,19 @@ hipError_t launch_phys_qtile_out(const DevGraph &g, const DevState &st, const QT
 }
 
 hipError_t launch_phys_qtile_count(const DevGraph &g, const DevState &st, const QTile &qt, unsigned long long *ctr,
-                                   hipStream_t s) {
+                                   hipStream_t s, const McStats &ms) {
     if (st.ntiles <= 0) return hipSuccess;
     const int per_tile = std::max(1, (g.k + 1023) >> 10);
-    phys_qtile_count_kernel<<<st.ntiles * per_tile, 64, 0, s>>>(g, st, qt, ctr);
+    phys_qtile_count_kernel<<<st.ntiles * per_tile, 64, 0, s>>>(g, st, qt, ctr, ms);
     return hipGetLastError();
 }
 
 hipError_t launch_phys_qtile_compact(const DevGraph &g, const DevState &st, const QTile &qt, bool flooding, int nt,
-                                     int cap, int *pairs, hipStream_t s) {
+                                     int cap, int *pairs, hipStream_t s, long long *slot_frame) {
     phys_qmark_counted_kernel<<<grid_for((size_t)st.ntiles * kTile, 256), 256, 0, s>>>(st);
     if (hipError_t e = launch_compact_plan(st, nt, cap, pairs, s)) return e;
     phys_qcompact_move_kernel<<<2048, 256, 0, s>>>(g, st, qt, flooding ? 1 : 0, cap, pairs);
-    phys_qcompact_flags_kernel<<<grid_for((size_t)cap, 256), 256, 0, s>>>(st, qt, cap, pairs);
+    phys_qcompact_flags_kernel<<<grid_for((size_t)cap, 256), 256, 0, s>>>(st, qt, cap, pairs, slot_frame);
     return hipGetLastError();
 }
 

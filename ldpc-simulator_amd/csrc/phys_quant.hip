@@ -62,6 +62,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
+#include <type_traits>
 
 #include "phys_common.h"
 #include "spa_device.h"
@@ -193,8 +194,9 @@ __device__ __forceinline__ int q_syndrome(const QuantArgs &a, const int16_t *L, 
 // Outputs and Monte-Carlo counters of frame f: frame_finish (phys_common.h) on
 // integer posteriors.  cnt: thread 0's running counts, FrameCounts::v or (to
 // spare 14 registers) a copy of it in LDS.
-__device__ __forceinline__ void q_frame_finish(const QuantArgs &a, int f, int conv, const int16_t *L, int *s_err,
-                                               int tid, int nt, unsigned long long *cnt) {
+template <bool STATS>
+__device__ __forceinline__ void q_frame_finish(const QuantArgs &a, const McStats &ms, int f, int conv, const int16_t *L, int *s_err,
+                                               unsigned *s_bins, int tid, int nt, unsigned long long *cnt) {
     const DevGraph &g = a.g;
     const int iters = conv >= 0 ? conv + 1 : a.max_iter;
     for (int j = tid; j < g.n; j += nt) {
@@ -209,7 +211,8 @@ __device__ __forceinline__ void q_frame_finish(const QuantArgs &a, int f, int co
     }
     if (a.ctr) {
         __syncthreads();
-        if (conv < 0) {  // BER counts failed frames only
+        constexpr bool stats = STATS;  // the statistics compare the converged frames too
+        if (conv < 0 || stats) {  // BER counts failed frames only
             const int kw = (g.k + 31) >> 5;
             int my = 0;
             for (int j = tid; j < g.k; j += nt) {
@@ -229,13 +232,14 @@ __device__ __forceinline__ void q_frame_finish(const QuantArgs &a, int f, int co
                 cnt[4] += 1ull;
             }
             cnt[6] += (unsigned long long)iters;
+            if constexpr (stats) mc_stats_frame(ms, ms.frame_base + f, conv, *s_err, s_bins);
         }
     }
     __syncthreads();  // LDS reused by the next frame
 }
 
-template <int CN, int SCHED>
-__global__ __launch_bounds__(512) void phys_quant_kernel(QuantArgs a) {
+template <int CN, int SCHED, bool STATS>
+__global__ __launch_bounds__(512) void phys_quant_kernel(QuantArgs a, McStats ms) {
     constexpr bool kLayered = SCHED == 1;
     extern __shared__ __attribute__((aligned(16))) uint32_t qlds[];
     const DevGraph &g = a.g;
@@ -244,8 +248,14 @@ __global__ __launch_bounds__(512) void phys_quant_kernel(QuantArgs a) {
     int8_t *Lam = reinterpret_cast<int8_t *>(L + ((g.n + 2) & ~1));      // [n], flooding only
     const int8_t *Eb = reinterpret_cast<const int8_t *>(E);
     __shared__ int s_err;
+    unsigned *s_bins = nullptr;
+    if constexpr (STATS) {  // static LDS of the statistics instantiation only
+        __shared__ unsigned bins[kMcBins];
+        s_bins = bins;
+    }
     FrameCounts fc;
     const int tid = threadIdx.x, nt = blockDim.x;
+    if constexpr (STATS) mc_stats_begin(s_bins, tid);
     for (int f = blockIdx.x; f < a.count; f += gridDim.x) {
         for (int j = tid; j < g.n; j += nt) {
             const int v = q_lambda(a, f, j);
@@ -298,9 +308,10 @@ __global__ __launch_bounds__(512) void phys_quant_kernel(QuantArgs a) {
                 }
             }
         }
-        q_frame_finish(a, f, conv, L, &s_err, tid, nt, fc.v);
+        q_frame_finish<STATS>(a, ms, f, conv, L, &s_err, s_bins, tid, nt, fc.v);
     }
     if (tid == 0) fc.flush(a.ctr);
+    if constexpr (STATS) mc_stats_flush(ms, s_bins, tid);
 }
 
 // The flooding decoder with every thread's rows and columns fixed for the whole
@@ -315,8 +326,8 @@ __global__ __launch_bounds__(512) void phys_quant_kernel(QuantArgs a) {
 // RW: dwords of a row (row degree <= 4 RW); CDEG: column degree bound.
 constexpr int kQRegNT = 512;
 
-template <int CN, int RPT, int RW, int CPT, int CDEG>
-__global__ __launch_bounds__(kQRegNT, 6) void phys_quant_reg_kernel(QuantArgs a) {
+template <int CN, int RPT, int RW, int CPT, int CDEG, bool STATS>
+__global__ __launch_bounds__(kQRegNT, 6) void phys_quant_reg_kernel(QuantArgs a, McStats ms) {
     extern __shared__ __attribute__((aligned(16))) uint32_t qlds[];
     const DevGraph &g = a.g;
     char *base = reinterpret_cast<char *>(qlds);  // E at 0, as phys_quant_kernel
@@ -325,7 +336,13 @@ __global__ __launch_bounds__(kQRegNT, 6) void phys_quant_reg_kernel(QuantArgs a)
     int8_t *Lam = reinterpret_cast<int8_t *>(L + ((g.n + 2) & ~1));
     __shared__ int s_err;
     __shared__ unsigned long long s_cnt[7];  // thread 0's FrameCounts
+    unsigned *s_bins = nullptr;
+    if constexpr (STATS) {  // static LDS of the statistics instantiation only
+        __shared__ unsigned bins[kMcBins];
+        s_bins = bins;
+    }
     const int tid = threadIdx.x;
+    if constexpr (STATS) mc_stats_begin(s_bins, tid);
     constexpr int NT = kQRegNT;
     if (tid < 7) s_cnt[tid] = 0ull;
     uint32_t rinfo[RPT];        // byte offset of the row's messages | degree << 16
@@ -459,13 +476,14 @@ __global__ __launch_bounds__(kQRegNT, 6) void phys_quant_reg_kernel(QuantArgs a)
                 }
             }
         }
-        q_frame_finish(a, f, conv, L, &s_err, tid, NT, s_cnt);
+        q_frame_finish<STATS>(a, ms, f, conv, L, &s_err, s_bins, tid, NT, s_cnt);
     }
     if (tid == 0 && a.ctr) {
 #pragma unroll
         for (int i = 0; i < 7; ++i)
             if (s_cnt[i]) atomicAdd(&a.ctr[i], s_cnt[i]);
     }
+    if constexpr (STATS) mc_stats_flush(ms, s_bins, tid);
 }
 
 }  // namespace
@@ -532,7 +550,7 @@ namespace {
 // than the seven resident evens out frames of unequal length (12.5 against
 // 13.3 ns at -2.5 dB), so it keeps the plain rule.
 template <typename K>
-void launch_quant(K kernel, const QuantArgs &a, int nt, size_t lds, int max_grid, bool resident, hipStream_t s) {
+void launch_quant(K kernel, const QuantArgs &a, const McStats &ms, int nt, size_t lds, int max_grid, bool resident, hipStream_t s) {
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
@@ -545,14 +563,14 @@ void launch_quant(K kernel, const QuantArgs &a, int nt, size_t lds, int max_grid
         (void)hipGetLastError();
     }
     const int grid = std::max(1, std::min(max_grid, cus * std::max(1, per_cu)));
-    kernel<<<grid, nt, lds, s>>>(a);
+    kernel<<<grid, nt, lds, s>>>(a, ms);
 }
 
-template <int CN>
-void launch_quant_reg(const QuantArgs &a, int shape, int max_grid, size_t lds, hipStream_t s) {
+template <int CN, bool STATS>
+void launch_quant_reg(const QuantArgs &a, const McStats &ms, int shape, int max_grid, size_t lds, hipStream_t s) {
     switch (shape) {
-    case 0: launch_quant(phys_quant_reg_kernel<CN, 1, 2, 2, 6>, a, kQRegNT, lds, max_grid, true, s); break;
-    default: launch_quant(phys_quant_reg_kernel<CN, 3, 2, 5, 6>, a, kQRegNT, lds, max_grid, true, s); break;
+    case 0: launch_quant(phys_quant_reg_kernel<CN, 1, 2, 2, 6, STATS>, a, ms, kQRegNT, lds, max_grid, true, s); break;
+    default: launch_quant(phys_quant_reg_kernel<CN, 3, 2, 5, 6, STATS>, a, ms, kQRegNT, lds, max_grid, true, s); break;
     }
 }
 
@@ -560,25 +578,33 @@ void launch_quant_reg(const QuantArgs &a, int shape, int max_grid, size_t lds, h
 
 hipError_t launch_phys_quant(const DevGraph &g, const double *llr, const float *lam, int count, int max_iter,
                              uint8_t *z, int *conv, int *status, int *iters, int16_t *post, const uint32_t *ubits,
-                             unsigned long long *ctr, int max_grid, hipStream_t s, const QuantRule &rule) {
+                             unsigned long long *ctr, int max_grid, hipStream_t s, const QuantRule &rule,
+                             const McStats &ms_in) {
     if (!rule.tab.row || !rule.tab.col || !rule.tab.csc || rule.qbits < 4 || rule.qbits > 8)
         return hipErrorInvalidValue;
     if (rule.cn != kCnNms && rule.cn != kCnOms) return hipErrorInvalidValue;
     const int qmax = (1 << (rule.qbits - 1)) - 1, pmax = (1 << (rule.qbits + 1)) - 1;
     QuantArgs a{g, llr, lam, count, max_iter, z, conv, status, iters, post, ubits, ctr, rule.tab, qmax, pmax,
                 rule.param_q, rule.scale, rule.layer_ptr, rule.layer_rows, rule.n_layers};
+    const McStats ms = ctr ? ms_in : McStats{};  // ms.hist set: the kernels' statistics instantiations
     if (count <= 0) return hipSuccess;
     const bool layered = rule.layer_ptr != nullptr;
     const size_t lds = phys_quant_lds_bytes(g, rule.tab.epad, layered);
     const int shape = phys_quant_reg_shape(g, rule.tab.epad, layered);
     const int nt = phys_quant_threads(g, rule);
     max_grid = std::min(max_grid, count);
-    if (shape >= 0 && rule.cn == kCnNms) launch_quant_reg<kCnNms>(a, shape, max_grid, lds, s);
-    else if (shape >= 0) launch_quant_reg<kCnOms>(a, shape, max_grid, lds, s);
-    else if (rule.cn == kCnNms && !layered) launch_quant(phys_quant_kernel<kCnNms, 0>, a, nt, lds, max_grid, false, s);
-    else if (rule.cn == kCnNms) launch_quant(phys_quant_kernel<kCnNms, 1>, a, nt, lds, max_grid, false, s);
-    else if (!layered) launch_quant(phys_quant_kernel<kCnOms, 0>, a, nt, lds, max_grid, false, s);
-    else launch_quant(phys_quant_kernel<kCnOms, 1>, a, nt, lds, max_grid, false, s);
+    const bool nms = rule.cn == kCnNms;
+    auto go = [&](auto stats) {  // stats: std::true_type for the kernels' statistics instantiations
+        constexpr bool S = decltype(stats)::value;
+        if (shape >= 0 && nms) launch_quant_reg<kCnNms, S>(a, ms, shape, max_grid, lds, s);
+        else if (shape >= 0) launch_quant_reg<kCnOms, S>(a, ms, shape, max_grid, lds, s);
+        else if (nms && !layered) launch_quant(phys_quant_kernel<kCnNms, 0, S>, a, ms, nt, lds, max_grid, false, s);
+        else if (nms) launch_quant(phys_quant_kernel<kCnNms, 1, S>, a, ms, nt, lds, max_grid, false, s);
+        else if (!layered) launch_quant(phys_quant_kernel<kCnOms, 0, S>, a, ms, nt, lds, max_grid, false, s);
+        else launch_quant(phys_quant_kernel<kCnOms, 1, S>, a, ms, nt, lds, max_grid, false, s);
+    };
+    if (ms.hist) go(std::true_type{});
+    else go(std::false_type{});
     return hipGetLastError();
 }
 

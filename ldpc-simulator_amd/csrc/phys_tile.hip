@@ -392,7 +392,7 @@ __global__ void phys_tile_out_kernel(DevGraph g, DevState st, PhysTile pt, uint8
 
 // main.py counters; block = one wavefront x (tile, 1024 info columns)
 __global__ __launch_bounds__(64) void phys_tile_count_kernel(DevGraph g, DevState st, PhysTile pt,
-                                                             unsigned long long *ctr) {
+                                                             unsigned long long *ctr, McStats ms) {
     const int kw = (g.k + 31) >> 5;
     const int per_tile = (g.k + 1023) >> 10 > 0 ? (g.k + 1023) >> 10 : 1;
     const int tile = blockIdx.x / per_tile, part = blockIdx.x % per_tile;
@@ -401,7 +401,9 @@ __global__ __launch_bounds__(64) void phys_tile_count_kernel(DevGraph g, DevStat
     const bool valid = st.done[f] == 1;  // finished and not counted yet (phys_tile_init, phys_compact)
     const bool failed = valid && st.status[f] != 0;
     unsigned long long err = 0;
-    if (__ballot(failed) != 0ull) {  // BER counts failed frames only (main.py:130-138)
+    // BER counts failed frames only (main.py:130-138); the statistics need the converged ones too
+    const bool cmp = ms.hist ? valid : failed;
+    if (__ballot(cmp) != 0ull) {
         const uint32_t *Ut = st.ubits + (size_t)tile * kw * kTile + lane;
         const float *Lt = pt.L + (size_t)tile * g.n * kTile + lane;
         const int j1 = min(g.k, (part + 1) * 1024);
@@ -409,10 +411,11 @@ __global__ __launch_bounds__(64) void phys_tile_count_kernel(DevGraph g, DevStat
             const uint32_t u = (Ut[(j >> 5) * kTile] >> (j & 31)) & 1u;
             err += (u != (Lt[j * kTile] < 0.0f ? 1u : 0u)) ? 1 : 0;
         }
-        if (!failed) err = 0;
+        if (!cmp) err = 0;
     }
-    const unsigned long long e = wave_sum(err);
+    const unsigned long long e = wave_sum(failed ? err : 0ull);
     if (lane == 0 && e) atomicAdd(&ctr[2], e);
+    if (ms.hist) mc_stats_tile(ms, st, tile, per_tile, lane, valid, failed, (int)err);
     if (part != 0) return;
     const int cv = valid ? st.conv[f] : -1;
     unsigned long long v[7] = {valid ? 1ull : 0ull, failed ? 1ull : 0ull, 0, cv >= 0 ? (unsigned long long)cv : 0,
@@ -423,6 +426,12 @@ __global__ __launch_bounds__(64) void phys_tile_count_kernel(DevGraph g, DevStat
         const unsigned long long s = wave_sum(v[i]);
         if (lane == 0 && s) atomicAdd(&ctr[i], s);
     }
+}
+
+// McStats::slot_frame of a fresh chunk
+__global__ void mc_stats_slots_kernel(long long *slot_frame, long long base, int count) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f < count) slot_frame[f] = base + f;
 }
 
 // Compaction (Monte-Carlo runs): after the finished frames were counted,
@@ -463,10 +472,12 @@ __global__ void phys_compact_move_kernel(DevGraph g, DevState st, PhysTile pt, i
         st.ubits[(dT * kw + it) * kTile + dl] = st.ubits[(sT * kw + it) * kTile + sl];
     }
 }
-__global__ void phys_compact_flags_kernel(DevState st, PhysTile pt, int cap, const int *pairs) {
+__global__ void phys_compact_flags_kernel(DevState st, PhysTile pt, int cap, const int *pairs,
+                                          long long *slot_frame) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= pairs[0]) return;
     const int src = pairs[1 + p], dst = pairs[1 + cap + p];
+    if (slot_frame) slot_frame[dst] = slot_frame[src];  // the frame's global index moves with it
     st.done[dst] = 0;
     st.conv[dst] = -1;
     st.status[dst] = 1;
@@ -762,18 +773,24 @@ hipError_t launch_phys_layer_exit(const DevGraph &g, const DevState &st, const P
 }
 
 hipError_t launch_phys_compact(const DevGraph &g, const DevState &st, const PhysTile &pt, int nt, int cap, int *pairs,
-                               hipStream_t s) {
+                               hipStream_t s, long long *slot_frame) {
     phys_mark_counted_kernel<<<grid_for((size_t)st.ntiles * kTile, 256), 256, 0, s>>>(st);
     if (hipError_t e = launch_compact_plan(st, nt, cap, pairs, s)) return e;
     phys_compact_move_kernel<<<2048, 256, 0, s>>>(g, st, pt, cap, pairs);
-    phys_compact_flags_kernel<<<grid_for((size_t)cap, 256), 256, 0, s>>>(st, pt, cap, pairs);
+    phys_compact_flags_kernel<<<grid_for((size_t)cap, 256), 256, 0, s>>>(st, pt, cap, pairs, slot_frame);
+    return hipGetLastError();
+}
+
+hipError_t launch_mc_stats_slots(long long *slot_frame, long long base, int count, hipStream_t s) {
+    if (!slot_frame || count <= 0) return hipSuccess;
+    mc_stats_slots_kernel<<<grid_for((size_t)count, 256), 256, 0, s>>>(slot_frame, base, count);
     return hipGetLastError();
 }
 
 hipError_t launch_phys_tile_count(const DevGraph &g, const DevState &st, const PhysTile &pt,
-                                  unsigned long long *ctr, hipStream_t s) {
+                                  unsigned long long *ctr, hipStream_t s, const McStats &ms) {
     const int per_tile = std::max(1, (g.k + 1023) >> 10);
-    phys_tile_count_kernel<<<st.ntiles * per_tile, 64, 0, s>>>(g, st, pt, ctr);
+    phys_tile_count_kernel<<<st.ntiles * per_tile, 64, 0, s>>>(g, st, pt, ctr, ms);
     return hipGetLastError();
 }
 

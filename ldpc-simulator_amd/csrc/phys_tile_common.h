@@ -6,6 +6,9 @@
 
 #include <algorithm>
 #include <cstddef>
+#include <cstdint>
+
+#include "spa_device.h"
 
 namespace ldpc {
 
@@ -29,6 +32,56 @@ __device__ __forceinline__ void xcd_item(int i, int per_tile, int &tile, int &pa
     const int slot = i >> 3;
     tile = (slot / per_tile) * 8 + (i & 7);
     part = slot % per_tile;
+}
+
+// Monte-Carlo statistics (McStats) of the frames a count kernel counts: one
+// wavefront per (tile, 1024 info columns), lane = slot of `tile`.  `valid`:
+// the slot's frame is finished and not counted yet (the same in every block of
+// the tile), so a frame is binned exactly once, at the end of its chunk or
+// before a compaction.  `err`: the info-bit errors of the lane's frame in this
+// block's columns -- with statistics on the count kernels compare every valid
+// lane, not only the failed ones: a converged frame that differs is an
+// undetected error.  The blocks of a tile add their shares to slot_err; the
+// one that arrives last (tile_arrive) takes the sums, leaves both arrays zero
+// and bins the tile's frames, each distinct bin with one atomic.
+__device__ __forceinline__ void mc_stats_tile(const McStats &ms, const DevState &st, int tile, int per_tile, int lane,
+                                              bool valid, bool failed, int err) {
+    const unsigned long long vmask = __ballot(valid);
+    if (vmask == 0ull) return;
+    const int f = tile * kTile + lane;
+    long long total = valid ? err : 0;
+    if (per_tile > 1) {
+        if (valid && err) atomicAdd(&ms.slot_err[f], err);
+        __threadfence();
+        int seen = 0;
+        if (lane == 0) seen = atomicAdd(&ms.tile_arrive[tile], 1);
+        if (__shfl(seen, 0) != per_tile - 1) return;
+        __threadfence();
+        if (lane == 0) atomicExch(&ms.tile_arrive[tile], 0);
+        total = valid ? atomicExch(&ms.slot_err[f], 0) : 0;
+    }
+    const int cv = valid && !failed ? st.conv[f] : ms.max_iter;
+    const int bin = min(max(cv, 0), ms.max_iter);
+    unsigned long long todo = vmask;
+    while (todo) {
+        const int b = __shfl(bin, __ffsll(todo) - 1);
+        const unsigned long long same = __ballot(valid && bin == b);
+        if (lane == 0) atomicAdd(&ms.hist[b], (unsigned long long)__popcll(same));
+        todo &= ~same;
+    }
+    const bool und = valid && !failed && total != 0;
+    const unsigned long long uf = wave_sum(und ? 1ull : 0ull), ub = wave_sum(und ? (unsigned long long)total : 0ull);
+    if (lane == 0 && uf) {
+        atomicAdd(&ms.und[0], uf);
+        atomicAdd(&ms.und[1], ub);
+    }
+    if (failed) {
+        const unsigned long long i = atomicAdd(&ms.und[2], 1ull);
+        if (i < (unsigned long long)ms.max_failed) {
+            ms.failed[2 * i] = ms.slot_frame[f];
+            ms.failed[2 * i + 1] = total;
+        }
+    }
 }
 
 inline unsigned grid_for(size_t total, int block) { return (unsigned)((total + block - 1) / block); }

@@ -211,13 +211,30 @@ struct PhysRule {
     bool layered_tile = false;      // layered: the HBM tile kernels (phys_tile.hip), not the LDS kernel
 };
 
+// Monte-Carlo statistics of one SNR point (ldpc_mc_stats_*), filled by every
+// physical-mode Monte-Carlo path as a frame finishes; hist == null: off.
+struct McStats {
+    unsigned long long *hist = nullptr;  // [max_iter + 1]: frames by conv; [max_iter]: failed frames
+    unsigned long long *und = nullptr;   // [0] undetected frames, [1] their info-bit errors, [2] failed frames seen
+                                         // (a failed frame reserves record und[2]++ and writes it if < max_failed)
+    long long *failed = nullptr;         // [max_failed][2]: global frame index, info-bit errors
+    long long *slot_frame = nullptr;     // tile paths: [cap] global frame index of the frame in each slot
+    int *slot_err = nullptr;             // tile paths: [cap] info-bit errors of a slot's frame, summed over the count
+                                         // kernel's blocks of the tile; zero between launches
+    int *tile_arrive = nullptr;          // tile paths: [cap / 64] blocks of the tile that added theirs; zero likewise
+    long long frame_base = 0;            // LDS paths: global frame index of the launch's frame 0
+    int max_failed = 0;
+    int max_iter = 0;
+};
+
 // physical mode (phys_kernels.hip)
 size_t phys_lds_bytes(const DevGraph &g);
 int phys_block_threads(const DevGraph &g);  // threads per workgroup launch_phys uses
 // layout 0: llr [count][n] fp64; 1: llr = ch tile layout; 2: lam [count][n] fp32 Lambda
 hipError_t launch_phys(const DevGraph &g, const double *llr, const float *lam, int layout, int count, int max_iter,
                        uint8_t *z, int *conv, int *status, int *iters, float *post, const uint32_t *ubits,
-                       unsigned long long *ctr, int grid, hipStream_t s, const PhysRule &rule = PhysRule{});
+                       unsigned long long *ctr, int grid, hipStream_t s, const PhysRule &rule = PhysRule{},
+                       const McStats &ms = McStats{});
 // layered min-sum (phys_layered.hip): E and L of a frame in LDS, one workgroup
 // barrier per layer; rule.cn is kCnNms or kCnOms and the layer table is set
 size_t phys_layered_lds_bytes(const DevGraph &g);
@@ -225,7 +242,7 @@ int phys_layered_threads(const PhysRule &rule);
 hipError_t launch_phys_layered(const DevGraph &g, const double *llr, const float *lam, int layout, int count,
                                int max_iter, uint8_t *z, int *conv, int *status, int *iters, float *post,
                                const uint32_t *ubits, unsigned long long *ctr, int grid, hipStream_t s,
-                               const PhysRule &rule);
+                               const PhysRule &rule, const McStats &ms = McStats{});
 
 // fixed-point min-sum with q-bit messages (phys_quant.hip): int8 E, int16 L and
 // (flooding) int8 Lam of a frame in LDS.  QuantTab is the graph's padded message
@@ -258,7 +275,8 @@ int phys_quant_threads(const DevGraph &g, const QuantRule &rule);
 // the device holds at once (CUs x resident per CU), at most max_grid and count.
 hipError_t launch_phys_quant(const DevGraph &g, const double *llr, const float *lam, int count, int max_iter,
                              uint8_t *z, int *conv, int *status, int *iters, int16_t *post, const uint32_t *ubits,
-                             unsigned long long *ctr, int max_grid, hipStream_t s, const QuantRule &rule);
+                             unsigned long long *ctr, int max_grid, hipStream_t s, const QuantRule &rule,
+                             const McStats &ms = McStats{});
 
 // physical mode, HBM-resident tiles + IRA frame source (phys_tile.hip)
 // on-device frames of a chunk (frame_kernels.hip): info bits -> st.ubits,
@@ -293,15 +311,18 @@ hipError_t launch_phys_layer_tile(const DevGraph &g, const DevState &st, const P
 // active_count[it], active_count[max_iter + it] (zeroed by the caller).
 hipError_t launch_phys_layer_exit(const DevGraph &g, const DevState &st, const PhysTile &pt, int it,
                                   int *active_count, int max_iter, hipStream_t s);
-// Monte-Carlo compaction of the running frames into tiles < nt (the finished ones counted first)
+// Monte-Carlo compaction of the running frames into tiles < nt (the finished ones counted first);
+// slot_frame (McStats, or null) moves with them
 hipError_t launch_phys_compact(const DevGraph &g, const DevState &st, const PhysTile &pt, int nt, int cap, int *pairs,
-                               hipStream_t s);
+                               hipStream_t s, long long *slot_frame = nullptr);
+// McStats::slot_frame of a freshly generated chunk: slot f holds frame base + f
+hipError_t launch_mc_stats_slots(long long *slot_frame, long long base, int count, hipStream_t s);
 hipError_t launch_phys_tile_final(const DevGraph &g, const DevState &st, const PhysTile &pt, int max_iter,
                                   hipStream_t s);
 hipError_t launch_phys_tile_out(const DevGraph &g, const DevState &st, const PhysTile &pt, uint8_t *z, float *post,
                                 hipStream_t s);
 hipError_t launch_phys_tile_count(const DevGraph &g, const DevState &st, const PhysTile &pt,
-                                  unsigned long long *ctr, hipStream_t s);
+                                  unsigned long long *ctr, hipStream_t s, const McStats &ms = McStats{});
 
 // fixed-point min-sum with the state in HBM (phys_qtile.hip): the tile layout
 // and the per-frame state (DevState, bad flags) of phys_tile.hip, the integers
@@ -337,9 +358,9 @@ hipError_t launch_phys_qtile_final(const DevGraph &g, const DevState &st, const 
 hipError_t launch_phys_qtile_out(const DevGraph &g, const DevState &st, const QTile &qt, uint8_t *z, int16_t *post,
                                  hipStream_t s);
 hipError_t launch_phys_qtile_count(const DevGraph &g, const DevState &st, const QTile &qt, unsigned long long *ctr,
-                                   hipStream_t s);
+                                   hipStream_t s, const McStats &ms = McStats{});
 hipError_t launch_phys_qtile_compact(const DevGraph &g, const DevState &st, const QTile &qt, bool flooding, int nt,
-                                     int cap, int *pairs, hipStream_t s);
+                                     int cap, int *pairs, hipStream_t s, long long *slot_frame = nullptr);
 
 // --- Philox4x32-10 (Salmon et al., SC'11), shared by host tests and device ---
 __host__ __device__ inline void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {

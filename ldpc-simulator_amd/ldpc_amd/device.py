@@ -245,6 +245,7 @@ class Decoder:
         self._h = h
         self._pid = os.getpid()
         self.capacity = int(_lib.gpu().ldpc_decoder_capacity(h))
+        self._max_failed = 0  # record capacity mc_stats_read offers: the max_failed of the last mc_stats()
 
     @staticmethod
     def workspace_bytes(graph, max_frames):
@@ -410,6 +411,37 @@ class Decoder:
         out = (ctypes.c_int64 * 2)()
         check("ldpc_fixed_point_read", _lib.gpu().ldpc_fixed_point_read(self._h, out))
         return int(out[0]), int(out[1])
+
+    def mc_stats(self, enable=True, max_failed=0):
+        """Collect the Monte-Carlo statistics of every phys_mc_run on this
+        decoder from now on (ldpc_mc_stats_enable): the histogram of the
+        convergence iteration, the undetected errors and up to max_failed
+        failed-frame records per SNR point.  The counters do not change."""
+        if int(max_failed) < 0:
+            raise ValueError(f"max_failed must be >= 0, got {max_failed}")
+        check("ldpc_mc_stats_enable", _lib.gpu().ldpc_mc_stats_enable(self._h, 1 if enable else 0, int(max_failed)))
+        self._max_failed = int(max_failed) if enable else 0
+
+    def mc_stats_read(self, point, max_iter):
+        """Statistics of SNR point `point` of the last phys_mc_run (max_iter as
+        in that run): {"hist": int64 [max_iter + 1] -- frames by convergence
+        iteration, the last bin the failed ones; "undetected_frames",
+        "undetected_bit_errors": frames that converged to other info bits than
+        were sent, and those bits; "failed": int64 [n, 2] (global frame index,
+        info-bit errors) sorted by index, at most max_failed; "failed_dropped":
+        failures beyond max_failed}.  Decoder.generate(seed, point, sigma,
+        index, 1) regenerates a listed frame."""
+        T = int(max_iter)
+        cap = self._max_failed
+        hist = np.zeros(T + 1, np.int64)
+        und = np.zeros(2, np.int64)
+        rec = np.zeros((cap, 2), np.int64)
+        nf = np.zeros(2, np.int64)
+        check("ldpc_mc_stats_read", _lib.gpu().ldpc_mc_stats_read(
+            self._h, int(point), _lib.ptr(hist), T + 1, _lib.ptr(und), _lib.ptr(rec) if cap else None, cap,
+            _lib.ptr(nf)))
+        return {"hist": hist, "undetected_frames": int(und[0]), "undetected_bit_errors": int(und[1]),
+                "failed": rec[:int(nf[0])].copy(), "failed_dropped": int(nf[1])}
 
     def close(self):
         h = getattr(self, "_h", None)

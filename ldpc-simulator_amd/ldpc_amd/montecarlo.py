@@ -68,8 +68,68 @@ def point_results(counters, k, snrs, matrix_path="", max_iter=5):
     return pts
 
 
+def fer_by_max_iter(hist):
+    """Detected FER for every iteration limit up to the run's, from one run's
+    histogram (Decoder.mc_stats_read): float64 [T], entry T' - 1 =
+    1 - sum_{t < T'} hist[t] / sum(hist), what a run with max_iter = T' over
+    the same frames reports -- a physical decoder's first T' iterations do not
+    depend on the limit.  All zeros for an empty histogram."""
+    hist = np.asarray(hist, dtype=np.int64)
+    T = len(hist) - 1
+    total = int(hist.sum())
+    if T < 1 or total == 0:
+        return np.zeros(max(T, 0), np.float64)
+    # (total - converged) / total in integers, one rounding: exactly the failed / frames of such a run
+    return (total - np.cumsum(hist[:T])).astype(np.float64) / float(total)
+
+
+def reduce_stats(stats, snrs, world=1, allreduce=None):
+    """Per-point statistics of a sweep from this rank's Decoder.mc_stats_read
+    dicts: with world > 1 the histograms and the undetected totals are summed
+    over the ranks (int64, the counters' allreduce).  Failure lists are per
+    rank and must be empty (max_failed = 0); failed_dropped is then every
+    failed frame, hist[T] of the summed histogram.  Then snr_db, frames and
+    fer_by_max_iter are added."""
+    stats = [dict(st) for st in stats]
+    if world > 1:
+        if allreduce is None:
+            raise ValueError("world > 1 needs an allreduce")
+        if any(len(st["failed"]) for st in stats):
+            raise ValueError("failed-frame lists are not gathered across ranks: max_failed must be 0 with world > 1")
+        T1 = len(stats[0]["hist"])
+        local = np.zeros((len(stats), T1 + 2), np.int64)
+        for row, st in zip(local, stats):
+            row[:T1] = st["hist"]
+            row[T1:] = st["undetected_frames"], st["undetected_bit_errors"]
+        total = np.asarray(allreduce(local), dtype=np.int64).reshape(local.shape)
+        for row, st in zip(total, stats):
+            st["hist"] = row[:T1].copy()
+            st["undetected_frames"], st["undetected_bit_errors"] = int(row[T1]), int(row[T1 + 1])
+            st["failed_dropped"] = int(row[T1 - 1])  # no records are kept: every failure of every rank
+    for snr, st in zip(snrs, stats):
+        st["hist"] = np.asarray(st["hist"], dtype=np.int64)
+        st["snr_db"] = float(snr)
+        st["frames"] = int(st["hist"].sum())
+        st["fer_by_max_iter"] = fer_by_max_iter(st["hist"])
+    return stats
+
+
+def stats_to_json(path, seed, stats):
+    """Write the statistics of a sweep (reduce_stats) with its seed: the seed
+    and a point's index and failed frame indices regenerate the failed frames."""
+    import json
+    pts = [{"snr_db": st["snr_db"], "frames": st["frames"], "hist": [int(x) for x in st["hist"]],
+            "fer_by_max_iter": [float(x) for x in st["fer_by_max_iter"]],
+            "undetected_frames": int(st["undetected_frames"]),
+            "undetected_bit_errors": int(st["undetected_bit_errors"]),
+            "failed": [[int(i), int(e)] for i, e in np.asarray(st["failed"]).reshape(-1, 2)],
+            "failed_dropped": int(st["failed_dropped"])} for st in stats]
+    with open(path, "w") as f:
+        json.dump({"seed": int(seed), "points": pts}, f, indent=1)
+
+
 def run_sweep(decoder, snrs, blocks, max_iter, seed=20260213, nllr=False, speed=1.0,
-              rank=0, world=1, allreduce=None, counter_fn=None):
+              rank=0, world=1, allreduce=None, counter_fn=None, stats_fn=None):
     """Counters [len(snrs), 7] for `blocks` frames per SNR point, summed over ranks.
 
     decoder     ldpc_amd.device.Decoder (its graph fixes the code) -- or None with counter_fn
@@ -77,6 +137,8 @@ def run_sweep(decoder, snrs, blocks, max_iter, seed=20260213, nllr=False, speed=
                 decoder.mc_run (the GPU path).  Tests inject a CPU stand-in to
                 exercise the sharding/all-reduce logic without a GPU.
     allreduce   callable(np.ndarray int64) -> summed array (ldpc_amd.comm.Comm.allreduce)
+    stats_fn    point index -> Decoder.mc_stats_read dict of the run counter_fn
+                just made; given, the result is (counters, reduce_stats(...))
     """
     sig = [sigma_for_snr(s, speed) for s in snrs]
     start, count = shard(int(blocks), rank, world)
@@ -88,6 +150,8 @@ def run_sweep(decoder, snrs, blocks, max_iter, seed=20260213, nllr=False, speed=
         if allreduce is None:
             raise ValueError("world > 1 needs an allreduce")
         local = np.asarray(allreduce(local), dtype=np.int64).reshape(len(snrs), NCOUNT)
+    if stats_fn is not None:
+        return local, reduce_stats([stats_fn(p) for p in range(len(snrs))], snrs, world, allreduce)
     return local
 
 
@@ -116,7 +180,8 @@ def decoder_type(cn_rule="spa", schedule="flooding", qbits=None):
 
 def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65536, device=0,
              rank=0, world=1, allreduce=None, matrix_path="", mode="parity", cn_rule="spa", schedule="flooding",
-             alpha=0.75, beta=0.5, qbits=None, llr_scale=4.0, layered_tile=False, quant_tile=False):
+             alpha=0.75, beta=0.5, qbits=None, llr_scale=4.0, layered_tile=False, quant_tile=False, stats=False,
+             max_failed=0):
     """Full sweep on this process's GPU -> SimulationResult (reference schema).
 
     mode "parity" is the reference's decoder on H_std; "physical" decodes the
@@ -129,11 +194,17 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
     the state fits LDS (it needs schedule="layered"; a code too large for LDS
     takes them anyway); quant_tile does the same for the fixed-point decoder
     (it needs qbits; either schedule).  matrix may name an IRA code (IRA_CODES): physical
-    mode only, the graph itself is the frame source."""
+    mode only, the graph itself is the frame source.
+    stats=True (physical mode) also collects the Monte-Carlo statistics and
+    returns (result, counters, stats): per point the Decoder.mc_stats_read dict
+    (up to max_failed failed-frame records) plus snr_db, frames and
+    fer_by_max_iter; with world > 1 the histograms and undetected totals are
+    summed over the ranks and max_failed must be 0."""
     from .code import EncoderDecoderData, load_committed_code
     from .device import Decoder, Graph, phys_flags, phys_quant_args, phys_rule_args
     if mode not in ("parity", "physical"):
         raise ValueError(f"mode must be 'parity' or 'physical', got {mode!r}")
+    check_stats_args(stats, max_failed, mode, world)
     phys_rule_args(cn_rule, schedule, alpha, beta)  # ValueError before any device call
     if mode == "parity" and (cn_rule, schedule) != ("spa", "flooding"):
         raise ValueError("cn_rule / schedule need mode='physical' (parity mode is the reference's sum-product)")
@@ -150,7 +221,7 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
         from . import ira
         return _simulate_graph(getattr(ira, IRA_CODES[matrix])(), matrix, t0, snrs, blocks, max_iter, seed, chunk,
                                device, rank, world, allreduce, matrix_path, cn_rule, schedule, alpha, beta, qbits,
-                               llr_scale, layered_tile, quant_tile)
+                               llr_scale, layered_tile, quant_tile, stats, max_failed)
     if isinstance(matrix, EncoderDecoderData):
         edd = matrix
     elif isinstance(matrix, str) and os.path.exists(matrix):
@@ -160,6 +231,8 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
     g = Graph(edd._h_std, device=device)
     dec = Decoder(g, Decoder.fit_slots(g, min(max(1, shard(int(blocks), rank, world)[1]), chunk)))
     counter_fn = None
+    if stats:
+        dec.mc_stats(True, max_failed)
     if mode == "physical":
         gp = Graph(edd.physical_matrix(), device=device)
 
@@ -168,7 +241,9 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
                                    alpha=alpha, beta=beta, qbits=qbits, llr_scale=llr_scale, tile=layered_tile,
                                    qtile=quant_tile)
     ctr = run_sweep(dec, snrs, blocks, max_iter, seed=seed, nllr=nllr, rank=rank, world=world,
-                    allreduce=allreduce, counter_fn=counter_fn)
+                    allreduce=allreduce, counter_fn=counter_fn,
+                    stats_fn=(lambda p: dec.mc_stats_read(p, max_iter)) if stats else None)
+    ctr, st = ctr if stats else (ctr, None)
     pts = point_results(ctr, edd._k, snrs, matrix_path=matrix_path or str(matrix), max_iter=max_iter)
     cfg = SimulationConfig(
         matrix_path=matrix_path or str(matrix), n=edd._n, m=edd._m, k=edd._k, rate=edd._rate,
@@ -176,11 +251,25 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
         interleaver_type="none", decoder_type=decoder_type(cn_rule, schedule, qbits), channel_mode=1, modulation=1,
         speed=1.0, snr_range=(snrs[0], snrs[-1], (snrs[1] - snrs[0]) if len(snrs) > 1 else 0.0),
         threads=world, timestamp=datetime.now().isoformat())
-    return SimulationResult(config=cfg, snr_points=pts, wall_clock_seconds=time.time() - t0), ctr
+    res = SimulationResult(config=cfg, snr_points=pts, wall_clock_seconds=time.time() - t0)
+    return (res, ctr, st) if stats else (res, ctr)
+
+
+def check_stats_args(stats, max_failed, mode, world):
+    """ValueError for statistics options simulate() cannot honour (before any device call)."""
+    if int(max_failed) < 0:
+        raise ValueError(f"max_failed must be >= 0, got {max_failed}")
+    if max_failed and not stats:
+        raise ValueError("max_failed needs stats=True")
+    if stats and mode != "physical":
+        raise ValueError("stats needs mode='physical' (parity mode collects no Monte-Carlo statistics)")
+    if stats and world > 1 and max_failed > 0:
+        raise ValueError("max_failed > 0 needs world == 1: failed-frame lists are not gathered across ranks")
 
 
 def _simulate_graph(H, name, t0, snrs, blocks, max_iter, seed, chunk, device, rank, world, allreduce, matrix_path,
-                    cn_rule, schedule, alpha, beta, qbits, llr_scale, layered_tile, quant_tile=False):
+                    cn_rule, schedule, alpha, beta, qbits, llr_scale, layered_tile, quant_tile=False, stats=False,
+                    max_failed=0):
     """simulate() in physical mode on an IRA graph H: one graph, the decoder's
     frame source and the graph it decodes on (as bench.py's config 5)."""
     from .device import Decoder, Graph
@@ -192,8 +281,11 @@ def _simulate_graph(H, name, t0, snrs, blocks, max_iter, seed, chunk, device, ra
     def counter_fn(sigmas, cnt, frame0):
         return dec.phys_mc_run(g, seed, sigmas, cnt, frame0, max_iter, cn=cn_rule, schedule=schedule, alpha=alpha,
                                beta=beta, qbits=qbits, llr_scale=llr_scale, tile=layered_tile, qtile=quant_tile)
+    if stats:
+        dec.mc_stats(True, max_failed)
     ctr = run_sweep(dec, snrs, blocks, max_iter, seed=seed, rank=rank, world=world, allreduce=allreduce,
-                    counter_fn=counter_fn)
+                    counter_fn=counter_fn, stats_fn=(lambda p: dec.mc_stats_read(p, max_iter)) if stats else None)
+    ctr, st = ctr if stats else (ctr, None)
     pts = point_results(ctr, k, snrs, matrix_path=matrix_path or name, max_iter=max_iter)
     cfg = SimulationConfig(
         matrix_path=matrix_path or name, n=n, m=m, k=k, rate=k / n, blocks=int(blocks),
@@ -201,7 +293,8 @@ def _simulate_graph(H, name, t0, snrs, blocks, max_iter, seed, chunk, device, ra
         decoder_type=decoder_type(cn_rule, schedule, qbits), channel_mode=1, modulation=1, speed=1.0,
         snr_range=(snrs[0], snrs[-1], (snrs[1] - snrs[0]) if len(snrs) > 1 else 0.0), threads=world,
         timestamp=datetime.now().isoformat())
-    return SimulationResult(config=cfg, snr_points=pts, wall_clock_seconds=time.time() - t0), ctr
+    res = SimulationResult(config=cfg, snr_points=pts, wall_clock_seconds=time.time() - t0)
+    return (res, ctr, st) if stats else (res, ctr)
 
 
 def build_parser():
@@ -233,6 +326,11 @@ def build_parser():
                     help="with --qbits: quantizer steps per unit of LLR (default 4)")
     ap.add_argument("--quant-tile", action="store_true",
                     help="with --qbits: the HBM tile kernels even where the quantized state fits LDS")
+    ap.add_argument("--stats-json", default=None, metavar="PATH",
+                    help="physical mode: write the per-point Monte-Carlo statistics (convergence histogram, "
+                         "FER by iteration limit, undetected errors, failed frames) to PATH")
+    ap.add_argument("--max-failed", type=int, default=0, metavar="N",
+                    help="with --stats-json: keep up to N failed-frame records per SNR point (default 0)")
     return ap
 
 
@@ -253,6 +351,12 @@ def parse_args(argv=None):
         ap.error("--llr-scale needs --qbits")
     if a.quant_tile and (a.mode != "physical" or a.qbits is None):
         ap.error("--quant-tile needs --mode physical --qbits")
+    if a.mode != "physical" and (a.stats_json is not None or a.max_failed != 0):
+        ap.error("--stats-json and --max-failed need --mode physical")
+    if a.max_failed != 0 and a.stats_json is None:
+        ap.error("--max-failed needs --stats-json")
+    if a.max_failed < 0:
+        ap.error("--max-failed must be >= 0")
     a.llr_scale = 4.0 if a.llr_scale is None else a.llr_scale
     a.alpha = 0.75 if a.alpha is None else a.alpha
     a.beta = 0.5 if a.beta is None else a.beta
@@ -278,10 +382,16 @@ def main(argv=None):
         comm = Comm.from_env(local)
         allreduce = comm.allreduce
     snrs = snr_grid(a.initial_snr, a.end_snr, a.step_snr)
-    res, _ = simulate(a.matrix, snrs, a.blocks, a.iterations, seed=a.seed, nllr=a.normalized_llr,
-                      device=local, rank=rank, world=world, allreduce=allreduce, mode=a.mode, cn_rule=a.cn_rule,
-                      schedule=a.schedule, alpha=a.alpha, beta=a.beta, qbits=a.qbits, llr_scale=a.llr_scale,
-                      layered_tile=a.layered_tile, quant_tile=a.quant_tile)
+    if world > 1 and a.max_failed > 0:
+        raise SystemExit("--max-failed needs a single process: failed-frame lists are not gathered across ranks")
+    out = simulate(a.matrix, snrs, a.blocks, a.iterations, seed=a.seed, nllr=a.normalized_llr,
+                   device=local, rank=rank, world=world, allreduce=allreduce, mode=a.mode, cn_rule=a.cn_rule,
+                   schedule=a.schedule, alpha=a.alpha, beta=a.beta, qbits=a.qbits, llr_scale=a.llr_scale,
+                   layered_tile=a.layered_tile, quant_tile=a.quant_tile, stats=a.stats_json is not None,
+                   max_failed=a.max_failed)
+    res = out[0]
+    if rank == 0 and a.stats_json is not None:
+        stats_to_json(a.stats_json, a.seed, out[2])
     if rank == 0:
         for sp in res.snr_points:
             print(f"SNR {sp.snr_db:.2f} dB  FER {sp.fer:.6f}  BER {sp.ber:.6e}  "

@@ -66,6 +66,9 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=3, help="timed steps per row (after one warm-up)")
     ap.add_argument("--alpha", type=float, default=0.75)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--mc-stats", type=int, default=None, metavar="MAX_FAILED",
+                    help="collect the Monte-Carlo statistics (Decoder.mc_stats) with this many failed-frame records "
+                         "per point: the cost of statistics on (default: off)")
     ap.add_argument("--out", help="also write the JSON line to this file")
     a = ap.parse_args(argv)
 
@@ -87,6 +90,8 @@ def main(argv=None):
         dec = Decoder(Graph(edd._h_std, device=a.device), B)  # frame source = H_std
         rows = (dict(cn="nms", schedule="layered"), dict(cn="nms", schedule="layered", tile=True))
         snrs = a.snrs or [-2.5, 1.0]
+    if a.mc_stats is not None:
+        dec.mc_stats(True, a.mc_stats)
     points = []
     for snr in snrs:
         sig = mc.sigma_for_snr(snr)
@@ -94,7 +99,7 @@ def main(argv=None):
                        "configs": [measure(dec, pg, sig, B, a.iters, a.steps, alpha=a.alpha, **r) for r in rows]})
     dec.close()
     line = json.dumps({"tool": "bench_phys_layered_tile", "which": a.which, "code": code, "frames_per_step": B,
-                       "steps": a.steps, "max_iter": a.iters, "alpha": a.alpha, "points": points})
+                       "steps": a.steps, "max_iter": a.iters, "alpha": a.alpha, "mc_stats": a.mc_stats, "points": points})
     print(line)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

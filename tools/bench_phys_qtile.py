@@ -71,6 +71,9 @@ def main(argv=None):
     ap.add_argument("--qbits", type=int, default=6)
     ap.add_argument("--llr-scale", type=float, default=2.0)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--mc-stats", type=int, default=None, metavar="MAX_FAILED",
+                    help="collect the Monte-Carlo statistics (Decoder.mc_stats) with this many failed-frame records "
+                         "per point: the cost of statistics on (default: off)")
     ap.add_argument("--out", help="also write the JSON line to this file")
     a = ap.parse_args(argv)
 
@@ -81,6 +84,8 @@ def main(argv=None):
     code, B = "dvbs2_profile_64800_0.5", a.frames
     pg = Graph(ira.dvbs2_profile_matrix(), device=a.device)
     dec = Decoder(pg, B)
+    if a.mc_stats is not None:
+        dec.mc_stats(True, a.mc_stats)
     q = dict(qbits=a.qbits, llr_scale=a.llr_scale)
     rows = (dict(cn="nms", schedule="flooding"), dict(cn="nms", schedule="layered"),
             dict(cn="nms", schedule="flooding", **q), dict(cn="nms", schedule="layered", **q))
@@ -91,7 +96,7 @@ def main(argv=None):
                        "configs": [measure(dec, pg, sig, B, a.iters, a.steps, alpha=a.alpha, **r) for r in rows]})
     dec.close()
     line = json.dumps({"tool": "bench_phys_qtile", "code": code, "n": pg.n, "edges": pg.nnz, "frames_per_step": B,
-                       "steps": a.steps, "max_iter": a.iters, "alpha": a.alpha, "qbits": a.qbits,
+                       "steps": a.steps, "max_iter": a.iters, "alpha": a.alpha, "mc_stats": a.mc_stats, "qbits": a.qbits,
                        "llr_scale": a.llr_scale, "points": points})
     print(line)
     if a.out:

@@ -41,6 +41,9 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=3, help="timed steps per configuration (after one warm-up)")
     ap.add_argument("--alpha", type=float, default=0.75)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--mc-stats", type=int, default=None, metavar="MAX_FAILED",
+                    help="collect the Monte-Carlo statistics (Decoder.mc_stats) with this many failed-frame records "
+                         "per point: the cost of statistics on (default: off)")
     ap.add_argument("--configs", nargs="+", default=["-".join(c) for c in CONFIGS],
                     choices=["-".join(c) for c in CONFIGS], help="rule-schedule pairs to run")
     ap.add_argument("--qbits", type=int, default=6, help="message bits of the quantized rows (0: none)")
@@ -57,6 +60,8 @@ def main(argv=None):
     g = Graph(edd._h_std, device=a.device)
     pg = Graph(edd.physical_matrix(), device=a.device)
     dec = Decoder(g, a.frames)  # frame source = H_std; the fp64 message arrays are never allocated
+    if a.mc_stats is not None:
+        dec.mc_stats(True, a.mc_stats)
     B = a.frames
     points = []
     for snr in a.snrs:
@@ -86,7 +91,7 @@ def main(argv=None):
         points.append({"snr_db": snr, "configs": rows, **({"quantized": qrows} if qrows else {})})
     dec.close()
     print(json.dumps({"tool": "bench_phys_rules", "code": a.code, "frames_per_step": B, "steps": a.steps,
-                      "max_iter": a.iters, "alpha": a.alpha, "points": points}))  # quantized rows: alpha_q = round(16 alpha)
+                      "max_iter": a.iters, "alpha": a.alpha, "mc_stats": a.mc_stats, "points": points}))  # quantized rows: alpha_q = round(16 alpha)
 
 
 if __name__ == "__main__":

@@ -387,10 +387,14 @@ int ldpc_rare_rows_read(ldpc_decoder *d, int64_t *out);
 /* Fixed-point exit of the static 16-frame sub-tile decoder (tile_sub_kernel:
  * wimax_2304_0.5): a frame whose pass reproduced its messages and posteriors
  * bit for bit stops there with the outputs it would have after max_iter passes
- * (status 1, conv -1, iters = max_iter).  Since the last call, then reset
- * (synchronises the device): out[0] = frames stopped this way, out[1] =
- * frame-passes they did not execute.  LDPC_FIXED_POINT=0 (environment, read
- * per launch) switches the exit off; results are identical either way. */
+ * (status 1, conv -1, iters = max_iter); so does a frame whose posteriors
+ * repeated and whose pass proved that the next one forms the same
+ * variable-to-check values bit for bit, although messages moved (tile_sub.hip
+ * "Fixed-point exit").  Since the last call, then reset (synchronises the
+ * device): out[0] = frames stopped this way, out[1] = frame-passes they did
+ * not execute.  LDPC_FIXED_POINT=0 (environment, read per launch) switches the
+ * exit off, LDPC_FP_NEXT=0 the second rule alone; results are identical
+ * either way. */
 int ldpc_fixed_point_read(ldpc_decoder *d, int64_t *out);
 
 /* ------------------------------------------- Monte-Carlo statistics

@@ -208,7 +208,9 @@ struct SubCtx {
     bool first, live;
     bool fresh;  // streaming: this lane's frame is on its first pass (M = L - 0, L = ch)
     bool verify;  // static decoder: this pass verifies a fixed point (sub_p3_body compares E_new with E_old)
-    int *mdiff;   // LDS [F]: verifying pass, a message of frame f differed
+    bool prove;   // ... and runs the next-pass proof where a message differed
+    int *mdiff;   // LDS [F]: verifying pass, bit 0: a message of frame f differed; bit 1: its next-pass proof failed
+                  // or went untested; bit 2: some frame's proof failed in this pass
     int ntiny;
 #ifdef LDPC_SUB_TIMERS
     mutable uint64_t tm[SUB_NT];
@@ -589,9 +591,30 @@ __device__ __forceinline__ void sub_p3_body(SubCtx<Q> &c, int r, double (&t)[Sub
         // are compared, so they have returned, before the stores issue.
         // Here and not ahead of the chain wait: E_old held from there costs 20
         // registers of every pass's row loop, this block none outside itself.
-        // Only the slots that differ are stored (the others at kSubOOB, which
-        // the hardware drops): memory holds E_new either way, and at a fixed
-        // point no slot differs -- the pass writes no message at all.
+        // Only the slots that differ are stored: memory holds E_new either
+        // way, and at a fixed point no slot differs -- the pass writes no
+        // message at all, and a wavefront none of whose lanes found a
+        // difference (nearly every one of such a pass) skips the rest of this
+        // block.
+        // The others run the next-pass proof before they store (c.prove).
+        // The posterior of each own slot's column is gathered, half of the
+        // slots at a time.  (Issued with the E_old reloads in every wavefront,
+        // the gathers spilled values of every pass's row loop and cost more
+        // than the exit won.)  During the row loop memory still holds L_old:
+        // the column sweep writes the A columns after it, this P3 the identity
+        // column k + r further down.  The variable-to-check value that this
+        // pass formed, L_old - E_old, is compared bit for bit with the one the
+        // next pass would form from E_new, and the identity column's new
+        // posterior, which the next pass would gather, with L_old.  A slot
+        // whose message repeated passes both tests as it stands (for iteration
+        // >= 1 the identity column's L = ch + (0 + E) repeats if E does);
+        // frame-less lanes and padded slots abstain.
+        // One failure anywhere in the workgroup ends the proof for this pass
+        // (bit 2 of every frame's flag; bit 1: this frame's own proof failed,
+        // or a difference of its went untested): the sub-tile runs on for the
+        // failing frame whatever the others prove, so the exit then takes no
+        // frame by the proof and the remaining rows gather nothing (where
+        // frames drift, that is after a row or two).
         const uint32_t eoff = sub_eoff(c, rc);
         const int njv = c.live ? nj : 0;
         double eold[K];
@@ -600,12 +623,40 @@ __device__ __forceinline__ void sub_p3_body(SubCtx<Q> &c, int r, double (&t)[Sub
             eold[i] = ld_sub_msg(c.rE, i < njv ? eoff + (uint32_t)i * (kTile * sizeof(double)) : kSubOOB);
         bool d = false;
 #pragma unroll
-        for (int i = 0; i < K; ++i) {
-            const bool di = i < njv && dbits(eold[i]) != dbits(t[i]);
-            d |= di;
-            st_sub_msg(c.rE, di ? eoff + (uint32_t)i * (kTile * sizeof(double)) : kSubOOB, t[i]);
+        for (int i = 0; i < K; ++i) d |= i < njv && dbits(eold[i]) != dbits(t[i]);
+        if (__builtin_expect(__ballot(d) != 0ull, 0)) {
+            constexpr int H = (K + 1) / 2;
+            bool nx = false;
+            // the flag only gains bits: a stale read costs one more test;
+            // without c.prove no frame is tested, and an untested difference
+            // counts as a failure
+            const bool open = c.prove && d && (lds_ld(c.mdiff + (threadIdx.x & (F - 1))) & 6) == 0;
+            if (__ballot(open) != 0ull) {
+#pragma unroll
+                for (int h = 0; h < K; h += H) {
+                    __builtin_amdgcn_sched_barrier(0);  // one half's gathers at a time
+                    double lo[H];
+#pragma unroll
+                    for (int i = 0; i < H; ++i)
+                        lo[i] = ld_l2((const double *)(c.Lu + sub_off(c, col[min(h + i, K - 1)])));
+#pragma unroll
+                    for (int i = 0; i < H; ++i)
+                        if (h + i < K) {
+                            const int q = h + i;
+                            nx |= q < njv && dbits(lo[i] - eold[q]) != dbits(lo[i] - t[q]);
+                            nx |= q < njv && col[q] >= c.k && dbits(chI + (0.0 + t[q])) != dbits(lo[i]);
+                        }
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < K; ++i) {
+                const bool di = i < njv && dbits(eold[i]) != dbits(t[i]);
+                st_sub_msg(c.rE, di ? eoff + (uint32_t)i * (kTile * sizeof(double)) : kSubOOB, t[i]);
+            }
+            if (d) atomicOr((uint32_t *)c.mdiff + (threadIdx.x & (F - 1)), (nx || !open) ? 3u : 1u);
+            // a failure: the proof of this pass is over for every frame of the workgroup
+            if (__ballot(nx) != 0ull && (threadIdx.x & 63) < F) atomicOr((uint32_t *)c.mdiff + (threadIdx.x & 63), 4u);
         }
-        if (d) atomicOr((uint32_t *)c.mdiff + (threadIdx.x & (F - 1)), 1u);
     } else {
         const uint32_t eoff = sub_eoff(c, rc);
 #pragma unroll
@@ -693,24 +744,50 @@ __device__ __forceinline__ void sub_body(SubCtx<Q> &c, int r, int m, double (&tc
 // deterministic function of (E, L) and ch, its summation order fixed by the
 // p3dep waits, so a frame whose pass reproduced E and L bit for bit repeats
 // that state on every later pass: it stops there with the outputs of pass
-// max_iter (failed frames at low SNR: the headline's frames stop after 3-5 of
+// max_iter (failed frames at low SNR: the headline's frames stop after 3 of
 // 50 passes).  Nothing approximate:
 //   trigger  the column sweep compares each A-column posterior with the
 //            previous one (ch on iteration 0) bit for bit: pdiffl[f];
 //   verify   a pass at iteration >= 1, when some running frame's posteriors
 //            repeated in the pass before, compares every own E_new with the
-//            E_old it replaces (c.verify, sub_p3_body): mdiffl[f], and stores
-//            only the ones that differ (at a fixed point: none).  The
+//            E_old it replaces (c.verify, sub_p3_body): bit 0 of mdiffl[f], and
+//            stores only the ones that differ (at a fixed point: none).  The
 //            identity columns need no check: for iteration >= 1
 //            L = ch + (0 + E) of the row's last edge repeats if E does;
-//   exit     after a verifying pass, a running frame with no message and no
-//            posterior difference in that pass (syndrome non-zero: a zero one
-//            took the OK exit) stops as DATA_TRANSFER_NOT_OK after max_iter
-//            iterations; its normalized-LLR history continues with the 0 that
-//            every later pass would count (ap == Lj);
-//   back-off a verifying pass that confirmed no frame is followed by a gap of
-//            1, 2, 4, ... passes before the next: at most 6 unconfirmed
-//            verifying passes (iterations 1, 3, 6, 11, 20, 37) at T = 50.
+//   proof    (bit 1 of fp; LDPC_FP_NEXT=0 switches this rule alone off) a
+//            verifying pass whose messages differed can still prove that the
+//            NEXT pass reproduces its output.  Pass `it` maps (E_old, L_old) to
+//            (E_new, L_new).  If L_new == L_old bit for bit on every column
+//            and, for every edge, fl(L_old[col] - E_new) has the bits of
+//            fl(L_old[col] - E_old), pass it + 1 forms exactly the
+//            variable-to-check values M that pass `it` formed, and everything
+//            after M -- the clamp, tanh, the chain product, the rare-row
+//            branch, the division, atanh, the S additions in p3dep order -- is
+//            a function of M in a fixed order: E and L after pass it + 1 are
+//            E_new and L_new, a fixed point from there on.  (A message far
+//            below its posterior's last bit moves without moving M: the
+//            headline's stragglers, whose sub-tiles ran a 4th pass for one or
+//            two frames.)  The A columns' half of "L_new == L_old" is the
+//            trigger's pdiffl[f]; sub_p3_body tests the rest where a message
+//            differed.  "No message differed" is the special case
+//            E_new == E_old.  The first failure in the workgroup (bit 2 of every
+//            frame's mdiffl) ends the proof for that pass: the sub-tile
+//            runs on for the failing frame whatever the others prove, so the
+//            rest of the pass gathers nothing and the pass takes no frame by
+//            the proof (the same frames whichever wavefront saw the flag when);
+//   exit     after a verifying pass, a running frame with no posterior
+//            difference in that pass and either no message difference or a
+//            proof that stood (syndrome non-zero: a zero one took the OK exit)
+//            stops as DATA_TRANSFER_NOT_OK after max_iter iterations, memory
+//            holding E_new and L_new; its normalized-LLR history continues
+//            with the 0 that every later pass would count (ap == Lj);
+//   back-off a verifying pass that stopped no frame is followed by a gap of
+//            1, 2, 4, ... passes before the next: at most 6 such verifying
+//            passes (iterations 1, 3, 6, 11, 20, 37) at T = 50.
+// The proof runs inside the verifying passes only, and those are scheduled as
+// before it existed.  (It holds for most headline frames after pass 1 already;
+// a verifying pass at iteration 1 happens only where a frame's posteriors
+// equalled ch after pass 0.)
 // st.fp_count: frames stopped this way, frame-passes not executed.
 template <int Q>
 __global__ __launch_bounds__(64 * kSW, 1) void tile_sub_kernel(DevGraph g, DevState st, int max_iter, int nllr,
@@ -718,7 +795,8 @@ __global__ __launch_bounds__(64 * kSW, 1) void tile_sub_kernel(DevGraph g, DevSt
                                                                const int *__restrict__ row_ptr, AtanhCoef ac, int fp) {
     constexpr int F = SubCfg<Q>::F, K = SubCfg<Q>::K;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    __shared__ int pdiffl[F], mdiffl[F];  // per frame: a posterior / a message differed in this pass
+    // per frame: a posterior differed in this pass / the bits of SubCtx::mdiff
+    __shared__ int pdiffl[F], mdiffl[F];
     const SubLayout ly = sub_layout(g.k, g.m, F);
     double *S = (double *)(lds + ly.S);
     MathLds &mlds = *(MathLds *)(lds + ly.math);
@@ -801,9 +879,14 @@ __global__ __launch_bounds__(64 * kSW, 1) void tile_sub_kernel(DevGraph g, DevSt
 
     // fixed-point exit, uniform over the workgroup: ctl = the word wavefront 0
     // left after the last pass (1: a frame still runs, 2: a running frame's
-    // posteriors repeated, 4: a frame stopped at a fixed point); the next
-    // verifying pass is allowed at iteration vnext, after a gap of vgap passes
+    // posteriors repeated, 4: a frame stopped at a fixed point, 8: one of them
+    // by the next-pass proof -- nothing reads 8, but without the ballot behind
+    // it this compiler spills two loop-invariant values of the normal passes'
+    // row loop: 19 scratch reloads per row pair there instead of none); the
+    // next verifying pass is allowed at iteration vnext, after a gap of vgap
+    // passes
     int ctl = 1, vnext = 1, vgap = 1;
+    const bool fpn = (fp & 2) != 0;  // the verifying passes also run the next-pass proof (LDPC_FP_NEXT)
     if (max_iter > 0) {  // iteration 0's tanh table, in L (sub_tanh_table); the other wavefronts gather it with ld_l2
         c.live = livel[f] != 0;
         sub_tanh_table<Q>(c, g.n, me, nthr);
@@ -816,6 +899,7 @@ __global__ __launch_bounds__(64 * kSW, 1) void tile_sub_kernel(DevGraph g, DevSt
         c.ep0 = sub_epoch0(it, m);
         const bool verify = fp != 0 && it >= vnext && (ctl & 2) != 0;
         c.verify = verify;
+        c.prove = verify && fpn;
         double tA[K], tB[K];
         bool yA = false, yB = false;
         if (m > 0) {
@@ -865,7 +949,7 @@ __global__ __launch_bounds__(64 * kSW, 1) void tile_sub_kernel(DevGraph g, DevSt
         __syncthreads();
 
         if (wave == 0) {  // per-frame exits, as vn_kernel (static schedule)
-            bool still = false, fixed = false;
+            bool still = false, fixed = false, proven = false;
             if (j == 0 && c.live) {
                 if (nllr) {
                     const int cn = cntl[f];
@@ -883,9 +967,11 @@ __global__ __launch_bounds__(64 * kSW, 1) void tile_sub_kernel(DevGraph g, DevSt
                     st.conv[fr] = -1;
                     st.status[fr] = 1;
                     st.iters[fr] = it + 1;
-                } else if (verify && mdiffl[f] == 0 && pdiffl[f] == 0) {
-                    // a fixed point: every pass up to max_iter - 1 would leave E, L and z as they
-                    // are, count 0 sign changes and end as DATA_TRANSFER_NOT_OK
+                } else if (verify && pdiffl[f] == 0 && ((mdiffl[f] & 1) == 0 || (mdiffl[f] & 6) == 0)) {
+                    // a fixed point, reached in this pass (no message differed) or proven for the next one
+                    // (every difference of the frame tested, and no frame's test failed in this pass): every
+                    // pass up to max_iter - 1 would leave E, L and z as memory holds them now,
+                    // count 0 sign changes and end as DATA_TRANSFER_NOT_OK
                     st.done[fr] = 1;
                     st.conv[fr] = -1;
                     st.status[fr] = 1;
@@ -893,6 +979,7 @@ __global__ __launch_bounds__(64 * kSW, 1) void tile_sub_kernel(DevGraph g, DevSt
                     if (nllr && st.nllr_hist)
                         for (int i = it + 1; i < max_iter; ++i) st.nllr_hist[(size_t)fr * st.hist_stride + i] = 0.0;
                     fixed = true;
+                    proven = mdiffl[f] != 0;
                 } else {
                     still = true;
                 }
@@ -900,6 +987,7 @@ __global__ __launch_bounds__(64 * kSW, 1) void tile_sub_kernel(DevGraph g, DevSt
             const unsigned long long any = __ballot(still);
             const unsigned long long trig = __ballot(still && fp && pdiffl[f] == 0);
             const int nfix = __popcll(__ballot(fixed));
+            const unsigned long long nprv = __ballot(proven);
             if (j == 0) {
                 livel[f] = still ? 1 : 0;
                 bad[f] = 0;
@@ -908,7 +996,7 @@ __global__ __launch_bounds__(64 * kSW, 1) void tile_sub_kernel(DevGraph g, DevSt
                 mdiffl[f] = 0;
             }
             if (lane == 0) {
-                flags[2 * kSR + 1] = (any != 0ull ? 1 : 0) | (trig != 0ull ? 2 : 0) | (nfix ? 4 : 0);
+                flags[2 * kSR + 1] = (any != 0ull ? 1 : 0) | (trig != 0ull ? 2 : 0) | (nfix ? 4 : 0) | (nprv != 0ull ? 8 : 0);
                 if (nfix) {
                     atomicAdd(&st.fp_count[0], (unsigned long long)nfix);
                     atomicAdd(&st.fp_count[1], (unsigned long long)nfix * (unsigned long long)(max_iter - 1 - it));
@@ -1019,6 +1107,7 @@ __global__ __launch_bounds__(64 * kSW, 1) void tile_sub_stream_kernel(
     c.ntiny = 0;
     c.first = false;
     c.verify = false;  // the fixed-point exit is the static decoder's
+    c.prove = false;
     c.mdiff = nullptr;
     const int m = g.m;
     const int nthr = kSW * Q;
@@ -1199,8 +1288,10 @@ hipError_t launch_tile_sub(const DevGraph &g, const DevState &st, int max_iter, 
     const size_t lds = sub_lds_bytes(g);
     if (!lds || 2 * st.ntiles > st.nslots) return hipErrorInvalidValue;  // two rare-row buffers per workgroup
     // LDPC_FIXED_POINT=0 (read per launch): no fixed-point exit, every frame makes its passes (A/B, diagnosis)
+    // LDPC_FP_NEXT=0 (bit 1 of fp): a frame stops only where no message differed, not on the next-pass proof
     const char *e = getenv("LDPC_FIXED_POINT");
-    const int fp = (!e || atoi(e) != 0) ? 1 : 0;
+    const char *en = getenv("LDPC_FP_NEXT");
+    const int fp = (!e || atoi(e) != 0) ? (1 | ((!en || atoi(en) != 0) ? 2 : 0)) : 0;
     tile_sub_kernel<4><<<st.ntiles * 4, 64 * kSW, lds, s>>>(g, st, max_iter, nllr ? 1 : 0, g.col_idx, g.row_ptr,
                                                             kAtanhCoef, fp);
     return hipGetLastError();

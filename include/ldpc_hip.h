@@ -33,7 +33,8 @@ extern "C" {
 
 #define LDPC_ABI_VERSION 5  /* 5: LDPC_F_TEST_ZERO + ldpc_rare_rows_read (4: profile kinds LDPC_K_NKINDS 11);
                              * ldpc_fixed_point_read was added under 5: an addition only, nothing else changed;
-                             * likewise ldpc_mc_stats_enable / ldpc_mc_stats_read: new symbols, the version stays 5 */
+                             * likewise ldpc_mc_stats_enable / ldpc_mc_stats_read and ldpc_channel_set /
+                             * ldpc_channel_get: new symbols, the version stays 5 */
 
 /* error codes */
 #define LDPC_OK 0
@@ -427,6 +428,76 @@ int ldpc_fixed_point_read(ldpc_decoder *d, int64_t *out);
 int ldpc_mc_stats_enable(ldpc_decoder *d, int32_t enable, int32_t max_failed);
 int ldpc_mc_stats_read(ldpc_decoder *d, int32_t point, int64_t *hist_out, int32_t hist_len,
                        int64_t *undetected_out, int64_t *failed_out, int32_t failed_cap, int64_t *n_failed_out);
+
+/* --------------------------------- channel models (physical mode only)
+ * The frame source above restates the reference's mode-1 channel: its noise
+ * standard deviation is sigma^2 and its SNR axis has no code-rate term.  That is
+ * what parity mode must reproduce.  For physical mode a decoder can carry a
+ * textbook channel instead, {model, modulation, demap} (new symbols under ABI 5:
+ * an addition only, the version stays 5):
+ *   model       LDPC_CH_REFERENCE  the source above, bit for bit (the default);
+ *                                  needs BPSK, demap is ignored;
+ *               LDPC_CH_AWGN       additive white Gaussian noise, h = 1;
+ *               LDPC_CH_RAYLEIGH   flat fading, an independent fade h per symbol
+ *                                  (BPSK: per bit), E[h^2] = 1, known to the receiver;
+ *   modulation  bits per symbol bps: 1 BPSK, 2 QPSK, 4 16-QAM, 6 64-QAM.  A code
+ *               with n % bps != 0 is LDPC_EINVAL when frames are generated;
+ *   demap       LDPC_DEMAP_EXACT or LDPC_DEMAP_MAXLOG.
+ * sigma under LDPC_CH_AWGN / LDPC_CH_RAYLEIGH is the noise standard deviation
+ * per real dimension at unit average symbol energy -- the true sigma, not
+ * sigma^2: N0 = 2 sigma^2 and Es/N0 = 1 / (2 sigma^2) for every modulation;
+ * Eb/N0 = Es/N0 / (rate * bps).
+ * Signs as everywhere: llr_j = ln P(y | b_j = 1) - ln P(y | b_j = 0), positive
+ * means bit 1; the decoders get Lambda = -(float)llr.
+ * Mapping: symbol s carries the codeword bits j = s*bps .. s*bps + bps - 1 in
+ * the frame's column order (H_std / IRA; a symbol may straddle the info/parity
+ * boundary k).  BPSK is real: x = +1 for bit 1, -1 for bit 0, noise on that one
+ * dimension.  QPSK / 16-QAM / 64-QAM are square and Gray mapped, the first
+ * bps/2 bits on the I axis, the rest on Q.  Per axis with bits a0 .. a(m-1),
+ * m = bps/2: binary b0 = a0, b_i = b_(i-1) xor a_i, B = sum b_i 2^(m-1-i), level
+ * (2B - (2^m - 1)) d with d = 1/sqrt(2), 1/sqrt(10), 1/sqrt(42):
+ *   a0a1:    00 -> -3d, 01 -> -d, 11 -> +d, 10 -> +3d;
+ *   a0a1a2:  000 -> -7d, 001 -> -5d, 011 -> -3d, 010 -> -d, 110 -> +d,
+ *            111 -> +3d, 101 -> +5d, 100 -> +7d.
+ * Draws (the Philox streams above, so a frame index still names one frame):
+ * the info bits are unchanged; the noise of symbol s is the N(0,1) pair of
+ * counter {F lo, F hi, s, (p<<1)|1}, g[0] on I and g[1] on Q; for BPSK bit j
+ * takes element j&1 of the pair j>>1, as the reference channel does; the fade
+ * of symbol (BPSK: bit) i comes from counter {F lo, F hi, 0x80000000 | (i>>1),
+ * (p<<1)|1}: u = the 52-bit uniform of words (0,1) for even i, of (2,3) for odd
+ * i, h = sqrt(-log u).
+ * Received value and LLR, all fp64: per axis r = h x + sigma g; the metric of
+ * level i is mu_i = (r - h x_i)^2 / (2 sigma^2);
+ *   exact    llr_t = LSE_{i: a_t(i)=1}(-mu_i) - LSE_{i: a_t(i)=0}(-mu_i), each
+ *            log-sum-exp with its maximum taken out first (finite for every
+ *            finite input);
+ *   max-log  llr_t = min_{a_t=0} mu_i - min_{a_t=1} mu_i;
+ *   one bit per axis (BPSK d = 1, QPSK): both are 2 h d r / sigma^2, computed
+ *   as that one expression, so the two demappers give identical bits.
+ * Example (16-QAM, AWGN, sigma = 0.5, I axis, bits a0a1 = 11 -> x = +d = 0.3162,
+ * g = 0.2 -> r = 0.4162): mu = (r - x_i)^2 / 0.5 = {3.726, 1.073, 0.020, 0.567}
+ * for the levels {-3d, -d, +d, +3d}; max-log llr_0 = 1.073 - 0.020 = 1.053 and
+ * llr_1 = 0.567 - 0.020 = 0.547.
+ * ldpc_channel_set validates the enums, reserved == 0 and REFERENCE => BPSK,
+ * then the decoder (NULL: LDPC_EINVAL); it does no device work.  ch == NULL puts
+ * the reference channel back.  The setting applies to ldpc_generate_frames,
+ * ldpc_phys_mc_run, _ex and _q on that decoder, so a failed-frame record of
+ * ldpc_mc_stats_read still regenerates with ldpc_generate_frames on the same
+ * decoder.  With a non-reference channel set, the parity-mode ldpc_mc_run and
+ * ldpc_frame_order are LDPC_EINVAL (the channel models are physical mode's), and
+ * so is LDPC_F_TEST_ZERO; all of these are checked before any device work.  The
+ * generated frames equal a numpy restatement over all 2^bps constellation
+ * points (tests/channel_ref.py). */
+#define LDPC_CH_REFERENCE 0
+#define LDPC_CH_AWGN 1
+#define LDPC_CH_RAYLEIGH 2
+#define LDPC_DEMAP_EXACT 0
+#define LDPC_DEMAP_MAXLOG 1
+typedef struct {
+    int32_t model, modulation, demap, reserved;
+} ldpc_channel;
+int ldpc_channel_set(ldpc_decoder *d, const ldpc_channel *ch);
+int ldpc_channel_get(const ldpc_decoder *d, ldpc_channel *out);
 
 /* ------------------------------------------------ multi-GPU (RCCL, xGMI)
  * One process per GPU; frames are sharded by global index, so the only

@@ -1,0 +1,259 @@
+// frame_channel_models.hip -- the frame source's channel models (physical mode
+// only; contract: include/ldpc_hip.h "channel models"), gfx950.  The last stage
+// of launch_frames (frame_kernels.hip) when a channel other than the reference's
+// is set: the codeword bits are the same (st.ubits, pt.pbits / pt.wpar), the
+// symbols, the noise scale and the LLRs are the textbook ones.
+//
+//   sigma     noise standard deviation per real dimension at unit average symbol
+//             energy: N0 = 2 sigma^2, Es/N0 = 1 / (2 sigma^2)
+//   BPSK      real, x = +-1, bit j takes noise_pair(j >> 1)[j & 1] as the
+//             reference channel does
+//   QPSK, 16-QAM, 64-QAM   square, Gray mapped per axis: symbol s carries bits
+//             s bps .. s bps + bps - 1, the first half on I, the rest on Q;
+//             noise_pair(s) = (I, Q)
+//   Rayleigh  h = sqrt(-log u), u from fade_uniforms (frame_source.h), one fade
+//             per symbol (BPSK: per bit), known to the receiver; AWGN: h = 1
+//   per axis  r = h x + sigma g,  mu_i = (r - h x_i)^2 / (2 sigma^2) over the
+//             2^(bps/2) levels x_i = (2 i - (2^m - 1)) d, Gray label i ^ (i >> 1)
+//   exact     llr_t = LSE_{a_t(i) = 1}(-mu_i) - LSE_{a_t(i) = 0}(-mu_i), each LSE
+//             with its own maximum taken out first
+//   max-log   llr_t = min_{a_t = 0} mu_i - min_{a_t = 1} mu_i
+//   one bit per axis (BPSK, QPSK): 2 h d r / sigma^2 for either demapper
+// All fp64; llr > 0 means bit 1; the decoders get Lambda = -(float)llr.
+//
+// A "unit" is what one Philox noise block serves: a symbol, or for BPSK the two
+// bits 2i, 2i+1.  Two forms, as frame_kernels.hip's:
+//   frame_model_kernel      lane = frame, a block walks 128 bits' worth of units
+//                           of one tile; every store is 64 consecutive frames
+//   frame_model_row_kernel  one wavefront per (frame, 64 units), lane = unit,
+//                           each lane writes its unit's consecutive fp32 Lambda
+// Both are bound by the fp64 log / sincospi / exp of a unit, not by their
+// stores; 64 threads per block as the reference kernels, so that a small chunk
+// still spreads over the chip.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+
+#include "frame_source.h"
+#include "spa_device.h"
+
+namespace ldpc {
+namespace {
+
+constexpr int kChRayleigh = 2;  // LDPC_CH_RAYLEIGH
+constexpr int kDemapMaxlog = 1;  // LDPC_DEMAP_MAXLOG
+
+// LLRs of the M Gray-labelled bits of one axis with 2^M levels, a_0 first.
+template <int M, int DEMAP>
+__device__ __forceinline__ void axis_llr(double r, double h, double s2, double *out) {
+    constexpr int L = 1 << M;
+    constexpr double d = M == 1 ? 0.70710678118654752440 : M == 2 ? 0.31622776601683793320 : 0.15430334996209191026;
+    if constexpr (M == 1) {
+        out[0] = 2.0 * h * d * r / s2;
+    } else {
+        double mu[L];
+#pragma unroll
+        for (int i = 0; i < L; ++i) {
+            const double t = r - h * ((double)(2 * i - (L - 1)) * d);
+            mu[i] = t * t / (2.0 * s2);
+        }
+#pragma unroll
+        for (int t = 0; t < M; ++t) {
+            double min0 = INFINITY, min1 = INFINITY;
+#pragma unroll
+            for (int i = 0; i < L; ++i) {
+                if (((i ^ (i >> 1)) >> (M - 1 - t)) & 1)
+                    min1 = fmin(min1, mu[i]);
+                else
+                    min0 = fmin(min0, mu[i]);
+            }
+            if constexpr (DEMAP == kDemapMaxlog) {
+                out[t] = min0 - min1;
+            } else {
+                double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+                for (int i = 0; i < L; ++i) {
+                    if (((i ^ (i >> 1)) >> (M - 1 - t)) & 1)
+                        s1 += exp(-(mu[i] - min1));
+                    else
+                        s0 += exp(-(mu[i] - min0));
+                }
+                out[t] = (log(s1) - min1) - (log(s0) - min0);
+            }
+        }
+    }
+}
+
+template <int BPS>
+struct Unit {
+    static constexpr int kAxisBits = BPS == 1 ? 1 : BPS / 2;
+    static constexpr int kBits = 2 * kAxisBits;       // BPSK: the two bits of a noise block
+    static constexpr int kPerBlock = 128 / kBits;     // units a block of the tile form walks
+    __host__ __device__ static int count(int n) { return BPS == 1 ? (n + 1) >> 1 : n / BPS; }
+};
+
+// llr[0 .. kBits) of unit i of frame F; a BPSK bit past n - 1 (odd n) gets 0.
+// BPSK is one real dimension with the levels +-1: the one-bit expression with d = 1.
+template <int BPS, int MODEL, int DEMAP>
+__device__ __forceinline__ void unit_llr(const uint32_t *Ut, const uint32_t *Pt, const uint32_t *Wt, int k, int n,
+                                         uint64_t seed, int64_t F, int snr_point, int i, double sigma, double *llr) {
+    constexpr int M = Unit<BPS>::kAxisBits;
+    constexpr int L = 1 << M;
+    constexpr double d = BPS == 1   ? 1.0
+                         : M == 1 ? 0.70710678118654752440
+                         : M == 2 ? 0.31622776601683793320
+                                  : 0.15430334996209191026;
+    const double s2 = sigma * sigma;
+    double g[2];
+    noise_pair(seed, F, snr_point, i, g);
+    double h[2] = {1.0, 1.0};
+    if constexpr (MODEL == kChRayleigh) {
+        double u[2];
+        if constexpr (BPS == 1) {
+            fade_uniforms(seed, F, snr_point, i, u);
+            h[0] = sqrt(-log(u[0]));
+            h[1] = sqrt(-log(u[1]));
+        } else {
+            fade_uniforms(seed, F, snr_point, i >> 1, u);
+            h[0] = h[1] = sqrt(-log((i & 1) ? u[1] : u[0]));
+        }
+    }
+    const int j0 = i * Unit<BPS>::kBits;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        if (BPS == 1 && j0 + q >= n) {
+            llr[q] = 0.0;
+            continue;
+        }
+        uint32_t a = 0u;  // the axis's Gray label, a_0 the most significant bit
+#pragma unroll
+        for (int t = 0; t < M; ++t) a = (a << 1) | frame_bit(Ut, Pt, Wt, k, j0 + q * M + t);
+        const int B = (int)(a ^ (a >> 1) ^ (a >> 2));  // b_i = b_(i-1) xor a_i (M <= 3)
+        const double x = (double)(2 * B - (L - 1)) * d;
+        const double r = h[q] * x + sigma * g[q];
+        if constexpr (BPS == 1)
+            llr[q] = 2.0 * h[q] * d * r / s2;
+        else
+            axis_llr<M, DEMAP>(r, h[q], s2, llr + q * M);
+    }
+}
+
+// to_lambda: the tile decoders' fp32 Lambda = L = -llr (kFramesTileLambda), else
+// the fp64 channel LLRs ch (kFramesCh).  Lanes past st.count write zeros.
+template <int BPS, int MODEL, int DEMAP>
+__global__ __launch_bounds__(64) void frame_model_kernel(DevGraph g, DevState st, PhysTile pt, uint64_t seed,
+                                                       int snr_point, double sigma, int64_t frame0, int to_lambda) {
+    using U = Unit<BPS>;
+    const int kw = (g.k + 31) >> 5;
+    const int mw = (g.m + 31) >> 5;
+    const int mw32 = (mw + 31) >> 5;
+    const int units = U::count(g.n);
+    const int per_tile = (units + U::kPerBlock - 1) / U::kPerBlock;
+    const int tile = blockIdx.x / per_tile;
+    const int i0 = (blockIdx.x % per_tile) * U::kPerBlock;
+    const int i1 = min(units, i0 + U::kPerBlock);
+    const int lane = threadIdx.x;
+    const int f = tile * kTile + lane;
+    const bool valid = f < st.count;
+    const int64_t F = frame0 + f;
+    const uint32_t *Ut = st.ubits + (size_t)tile * kw * kTile + lane;
+    const uint32_t *Pt = pt.pbits + (size_t)tile * mw * kTile + lane;
+    const uint32_t *Wt = pt.wpar + (size_t)tile * mw32 * kTile + lane;
+    double *Ct = st.ch + (size_t)tile * g.n * kTile + lane;
+    float *Lamt = pt.Lam + (size_t)tile * g.n * kTile + lane;
+    float *Lt = pt.L + (size_t)tile * g.n * kTile + lane;
+    for (int i = i0; i < i1; ++i) {
+        double llr[U::kBits];
+        unit_llr<BPS, MODEL, DEMAP>(Ut, Pt, Wt, g.k, g.n, seed, F, snr_point, i, sigma, llr);
+#pragma unroll
+        for (int t = 0; t < U::kBits; ++t) {
+            const int j = i * U::kBits + t;
+            if (j >= g.n) break;
+            const double v = valid ? llr[t] : 0.0;
+            if (to_lambda) {
+                Lamt[j * kTile] = -(float)v;
+                Lt[j * kTile] = -(float)v;
+            } else {
+                Ct[j * kTile] = v;
+            }
+        }
+    }
+}
+
+// Row-major fp32 Lambda = -llr, [count][n] (kFramesRowLambda).
+template <int BPS, int MODEL, int DEMAP>
+__global__ __launch_bounds__(64) void frame_model_row_kernel(DevGraph g, DevState st, PhysTile pt, uint64_t seed,
+                                                           int snr_point, double sigma, int64_t frame0,
+                                                           float *__restrict__ row_out) {
+    using U = Unit<BPS>;
+    const int kw = (g.k + 31) >> 5;
+    const int mw = (g.m + 31) >> 5;
+    const int mw32 = (mw + 31) >> 5;
+    const int units = U::count(g.n);
+    const int per_frame = (units + 63) >> 6;
+    const int f = blockIdx.x / per_frame;
+    const int i = (blockIdx.x % per_frame) * 64 + threadIdx.x;
+    if (f >= st.count || i >= units) return;
+    const int tile = f >> 6, lf = f & 63;
+    const uint32_t *Ut = st.ubits + (size_t)tile * kw * kTile + lf;
+    const uint32_t *Pt = pt.pbits + (size_t)tile * mw * kTile + lf;
+    const uint32_t *Wt = pt.wpar + (size_t)tile * mw32 * kTile + lf;
+    double llr[U::kBits];
+    unit_llr<BPS, MODEL, DEMAP>(Ut, Pt, Wt, g.k, g.n, seed, frame0 + f, snr_point, i, sigma, llr);
+    float *row = row_out + (size_t)f * g.n;
+#pragma unroll
+    for (int t = 0; t < U::kBits; ++t) {
+        const int j = i * U::kBits + t;
+        if (j >= g.n) break;
+        row[j] = -(float)llr[t];
+    }
+}
+
+template <int BPS, int MODEL, int DEMAP>
+hipError_t launch_model(const DevGraph &g, const DevState &st, const PhysTile &pt, uint64_t seed, int snr_point,
+                        double sigma, int64_t frame0, FramesOut out, float *row_out, hipStream_t s) {
+    using U = Unit<BPS>;
+    const int units = U::count(g.n);
+    if (out == kFramesRowLambda)
+        frame_model_row_kernel<BPS, MODEL, DEMAP><<<st.count * ((units + 63) >> 6), 64, 0, s>>>(
+            g, st, pt, seed, snr_point, sigma, frame0, row_out);
+    else
+        frame_model_kernel<BPS, MODEL, DEMAP><<<st.ntiles * ((units + U::kPerBlock - 1) / U::kPerBlock), 64, 0, s>>>(
+            g, st, pt, seed, snr_point, sigma, frame0, out == kFramesTileLambda ? 1 : 0);
+    return hipGetLastError();
+}
+
+// One bit per axis has one LLR expression: a single instantiation serves both demappers.
+template <int MODEL>
+hipError_t launch_model_of(const DevGraph &g, const DevState &st, const PhysTile &pt, uint64_t seed, int snr_point,
+                           double sigma, int64_t frame0, FramesOut out, float *row_out, const FrameChannel &ch,
+                           hipStream_t s) {
+    const bool maxlog = ch.demap == kDemapMaxlog;
+    switch (ch.bps) {
+        case 1: return launch_model<1, MODEL, 0>(g, st, pt, seed, snr_point, sigma, frame0, out, row_out, s);
+        case 2: return launch_model<2, MODEL, 0>(g, st, pt, seed, snr_point, sigma, frame0, out, row_out, s);
+        case 4:
+            return maxlog ? launch_model<4, MODEL, 1>(g, st, pt, seed, snr_point, sigma, frame0, out, row_out, s)
+                          : launch_model<4, MODEL, 0>(g, st, pt, seed, snr_point, sigma, frame0, out, row_out, s);
+        case 6:
+            return maxlog ? launch_model<6, MODEL, 1>(g, st, pt, seed, snr_point, sigma, frame0, out, row_out, s)
+                          : launch_model<6, MODEL, 0>(g, st, pt, seed, snr_point, sigma, frame0, out, row_out, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_frame_channel_model(const DevGraph &g, const DevState &st, const PhysTile &pt, uint64_t seed,
+                                      int snr_point, double sigma, int64_t frame0, FramesOut out, float *row_out,
+                                      const FrameChannel &ch, hipStream_t s) {
+    if (ch.bps < 1 || g.n % ch.bps != 0 || st.count <= 0) return hipErrorInvalidValue;
+    if (ch.model == kChRayleigh)
+        return launch_model_of<kChRayleigh>(g, st, pt, seed, snr_point, sigma, frame0, out, row_out, ch, s);
+    if (ch.model == 1)  // LDPC_CH_AWGN
+        return launch_model_of<1>(g, st, pt, seed, snr_point, sigma, frame0, out, row_out, ch, s);
+    return hipErrorInvalidValue;
+}
+
+}  // namespace ldpc

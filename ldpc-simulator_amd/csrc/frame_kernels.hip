@@ -12,7 +12,9 @@
 //                   parities: p_r = p_{r-1} ^ s_r, the accumulator
 //   frame_channel   bit -> BPSK -> + sigma^2 N(0,1) -> llr = 2y/sigma^2, written as
 //                   fp64 ch (parity decoder, LDS physical decoder, export) or as
-//                   the tile physical decoder's fp32 Lambda = L = -llr
+//                   the tile physical decoder's fp32 Lambda = L = -llr; under a
+//                   channel model (physical mode: ldpc_channel_set) this last
+//                   stage is frame_channel_models.hip's instead
 // Every kernel has >= ntiles x (n/128 or m/128) wavefronts, so even a small
 // chunk fills the chip (the streaming refill, where single slots are
 // regenerated, uses frame_source.h's gen_slots: the same draws).
@@ -137,10 +139,7 @@ __global__ __launch_bounds__(64) void frame_channel_kernel(DevGraph g, DevState 
         for (int q = 0; q < 2; ++q) {
             const int j = 2 * b + q;
             if (j >= g.n) break;
-            const int r = j - g.k;
-            const int w = r >> 5;
-            const uint32_t bit = j < g.k ? (Ut[(j >> 5) * kTile] >> (j & 31)) & 1u
-                                         : ((Pt[w * kTile] >> (r & 31)) ^ (Wt[(w >> 5) * kTile] >> (w & 31))) & 1u;
+            const uint32_t bit = frame_bit(Ut, Pt, Wt, g.k, j);
             const double llr = valid && !test_zero_llr(g, F, j) ? channel_llr(bit, gz[q], s2) : 0.0;
             if (to_lambda) {
                 Lamt[j * kTile] = -(float)llr;
@@ -178,10 +177,7 @@ __global__ __launch_bounds__(64) void frame_channel_row_kernel(DevGraph g, DevSt
     for (int q = 0; q < 2; ++q) {
         const int j = 2 * b + q;
         if (j >= g.n) break;
-        const int r = j - g.k;
-        const int w = r >> 5;
-        const uint32_t bit = j < g.k ? (Ut[(j >> 5) * kTile] >> (j & 31)) & 1u
-                                     : ((Pt[w * kTile] >> (r & 31)) ^ (Wt[(w >> 5) * kTile] >> (w & 31))) & 1u;
+        const uint32_t bit = frame_bit(Ut, Pt, Wt, g.k, j);
         row_out[(size_t)f * g.n + j] = test_zero_llr(g, frame0 + f, j) ? -0.0f : -(float)channel_llr(bit, gz[q], s2);
     }
 }
@@ -228,7 +224,8 @@ __global__ __launch_bounds__(256) void std_parity_kernel(DevGraph g, DevState st
 }  // namespace
 
 hipError_t launch_frames(const DevGraph &g, const DevState &st, const PhysTile &pt, uint64_t seed, int snr_point,
-                         double sigma, int64_t frame0, FramesOut out, float *row_out, hipStream_t s) {
+                         double sigma, int64_t frame0, FramesOut out, float *row_out, const FrameChannel &ch,
+                         hipStream_t s) {
     const int kw = (g.k + 31) >> 5, mw = (g.m + 31) >> 5;
     const int nblk = (kw + 3) >> 2, bpb = 16;
     const int nbc = (nblk + bpb - 1) / bpb;
@@ -248,6 +245,8 @@ hipError_t launch_frames(const DevGraph &g, const DevState &st, const PhysTile &
         else
             std_parity_kernel<0><<<grid, 256, 0, s>>>(g, st, pt, g.a_packed);
     }
+    // a channel model (physical mode only): the same bits, its own last stage
+    if (ch.model != 0) return launch_frame_channel_model(g, st, pt, seed, snr_point, sigma, frame0, out, row_out, ch, s);
     const int npairs = (g.n + 1) >> 1;
     if (out == kFramesRowLambda)
         frame_channel_row_kernel<<<st.count * ((npairs + 63) >> 6), 64, 0, s>>>(g, st, pt, seed, snr_point, sigma,

@@ -6,6 +6,8 @@
 //     {F lo, F hi, w/4, p<<1}, word w%4 of the output
 //   noise of columns 2b, 2b+1: counter {F lo, F hi, b, (p<<1)|1}, two 52-bit
 //     uniforms, Box-Muller r*cos / r*sin
+//   fade of symbols 2b, 2b+1 (channel models only): counter {F lo, F hi,
+//     0x80000000 | b, (p<<1)|1}, two 52-bit uniforms
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -45,12 +47,35 @@ __device__ __forceinline__ void noise_pair(uint64_t seed, int64_t F, int snr_poi
     g[1] = r * sn;
 }
 
+// Fade uniforms of symbols (BPSK: bits) 2*b and 2*b+1 of frame F (the channel
+// models of frame_channel_models.hip): the noise counter with bit 31 of word 2
+// set, so no noise block shares it; h = sqrt(-log(u)), E[h^2] = 1.
+__device__ __forceinline__ void fade_uniforms(uint64_t seed, int64_t F, int snr_point, int b, double u[2]) {
+    uint32_t c[4] = {(uint32_t)F, (uint32_t)((uint64_t)F >> 32), 0x80000000u | (uint32_t)b,
+                     ((uint32_t)snr_point << 1) | 1u};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    u[0] = u52(c[0], c[1]);
+    u[1] = u52(c[2], c[3]);
+}
+
 // BPSK bit0 -> -1, bit1 -> +1 (channel.py:49); y = x + sigma^2 g (noise std is
 // sigma^2, channel.py:68-76); llr = 2y/sigma^2 (channel.py:80).
 __device__ __forceinline__ double channel_llr(uint32_t bit, double g, double s2) {
     const double x = bit ? 1.0 : -1.0;
     const double y = x + s2 * g;
     return (2.0 * y) / s2;
+}
+
+// Codeword bit j of one frame from the generator's tile-layout words (lane =
+// frame, stride kTile; the pointers already offset to the frame's lane): an
+// info bit of ubits, else parity r = j - k as bit r%32 of pbits[r/32] ^ wpar bit
+// r/32 (frame_kernels.hip: std_parity / ira_sbits + ira_carry).
+__device__ __forceinline__ uint32_t frame_bit(const uint32_t *Ut, const uint32_t *Pt, const uint32_t *Wt, int k,
+                                              int j) {
+    const int r = j - k;
+    const int w = r >> 5;
+    return j < k ? (Ut[(j >> 5) * kTile] >> (j & 31)) & 1u
+                 : ((Pt[w * kTile] >> (r & 31)) ^ (Wt[(w >> 5) * kTile] >> (w & 31))) & 1u;
 }
 
 // Test-only erasures (LDPC_F_TEST_ZERO; tests/test_gpu_rare_stream.py): with

@@ -118,6 +118,8 @@ struct ldpc_decoder {
     int *ms_tile = nullptr;             // tile paths: slot_err [cap], then tile_arrive [cap_tiles] (McStats)
     int ms_state = 0;  // 0: nothing to read, 1: the last physical run's statistics, 2: the last run was ldpc_mc_run
     int ms_points = 0, ms_T = 0, ms_run_failed = 0;  // of the run in ms_buf
+    // the frame source's channel (ldpc_channel_set); the default is the reference's
+    ldpc::FrameChannel chan{};
     // profiling (ldpc_profile_*)
     bool prof = false;
     struct Span {
@@ -291,6 +293,28 @@ DevGraph call_graph(const ldpc_decoder *d, uint32_t flags) {
     DevGraph G = d->g->dg;
     G.zinj = (flags & LDPC_F_TEST_ZERO) ? 1 : 0;
     return G;
+}
+
+// What a call that generates frames under the decoder's channel model must
+// hold (no device work): the code length divides into symbols, and the
+// test-only erasures belong to the reference channel.
+int channel_frames_check(const char *fn, const ldpc_decoder *d, uint32_t flags) {
+    if (d->chan.model == LDPC_CH_REFERENCE) return LDPC_OK;
+    const int n = d->g->dg.n;
+    if (n % d->chan.bps != 0)
+        return ldpc_fail(LDPC_EINVAL, "%s: n = %d is not a multiple of bps = %d (the channel's bits per symbol)", fn, n,
+                         d->chan.bps);
+    if (flags & LDPC_F_TEST_ZERO)
+        return ldpc_fail(LDPC_EINVAL, "%s: LDPC_F_TEST_ZERO (test erasures) needs the reference channel, this decoder "
+                                      "has a channel model set (ldpc_channel_set)", fn);
+    return LDPC_OK;
+}
+
+// The parity-mode entries reproduce the reference: its channel only.
+int channel_parity_check(const char *fn, const ldpc_decoder *d) {
+    if (d->chan.model == LDPC_CH_REFERENCE) return LDPC_OK;
+    return ldpc_fail(LDPC_EINVAL, "%s: parity mode has the reference channel only; the channel models are physical "
+                                  "mode's (ldpc_channel_set(d, NULL) puts the reference channel back)", fn);
 }
 
 hipEvent_t take_event(ldpc_decoder *d) {
@@ -961,6 +985,7 @@ int ldpc_generate_frames(ldpc_decoder *d, uint64_t seed, int32_t snr_point, doub
     if (count < 0 || count > d->cap_tiles * kTile || snr_point < 0 || frame0 < 0 || !(sigma > 0.0))
         return ldpc_fail(LDPC_EINVAL, "ldpc_generate_frames: bad arguments (count=%d cap=%d)", count,
                          d->cap_tiles * kTile);
+    if (int rc = channel_frames_check("ldpc_generate_frames", d, flags)) return rc;
     if (count == 0) return LDPC_OK;
     DeviceGuard dg(d->g->device);
     hipStream_t s = (hipStream_t)stream;
@@ -981,7 +1006,7 @@ int ldpc_generate_frames(ldpc_decoder *d, uint64_t seed, int32_t snr_point, doub
         return rc;
     }
     HIP_TRY(ldpc::launch_frames(G, d->st, phys_tile(d), seed, snr_point, sigma, frame0, ldpc::kFramesCh, nullptr,
-                                s));
+                                d->chan, s));
     // export writes u only for j<k, at [f][k]: give it the [count][k] buffer
     HIP_TRY(ldpc::launch_export_frames(G, d->st, u_dev, l_dev, s));
     if (!dev_ptrs) {
@@ -1202,6 +1227,7 @@ int ldpc_frame_order(ldpc_decoder *d, uint64_t seed, int32_t snr_point, double s
                      int32_t count, int32_t *order_out, void *stream) {
     if (!d || count < 0 || snr_point < 0 || frame0 < 0 || !(sigma > 0.0) || (count > 0 && !order_out))
         return ldpc_fail(LDPC_EINVAL, "ldpc_frame_order: bad arguments");
+    if (int rc = channel_parity_check("ldpc_frame_order", d)) return rc;
     const DevGraph &G = d->g->dg;
     if (!G.std_form || !G.a_packed || G.m > 65535)
         return ldpc_fail(LDPC_EINVAL, "ldpc_frame_order: graph is not [A | I_m] with m <= 65535");
@@ -1220,6 +1246,7 @@ int ldpc_mc_run(ldpc_decoder *d, uint64_t seed, int32_t n_points, const double *
                 int64_t frame0, int32_t max_iter, uint32_t flags, int64_t *counters_out, void *stream) {
     if (!d || n_points <= 0 || !sigmas || frames_per_point < 0 || frame0 < 0 || max_iter < 1 || !counters_out)
         return ldpc_fail(LDPC_EINVAL, "ldpc_mc_run: bad arguments");
+    if (int rc = channel_parity_check("ldpc_mc_run", d)) return rc;
     const DevGraph G = call_graph(d, flags);
     if (!G.std_form) return ldpc_fail(LDPC_EINVAL, "ldpc_mc_run: graph is not [A | I_m]");
     for (int p = 0; p < n_points; ++p)
@@ -1254,7 +1281,8 @@ int ldpc_mc_run(ldpc_decoder *d, uint64_t seed, int32_t n_points, const double *
                 const DevState st = d->st;
                 HIP_TRY(timed(d, LDPC_K_GEN, s,
                               [&] { return ldpc::launch_frames(G, st, phys_tile(d), seed, p, sigmas[p], frame0 + start,
-                                                               ldpc::kFramesCh, nullptr, s); }));
+                                                               ldpc::kFramesCh, nullptr, ldpc::FrameChannel{},
+                                                               s); }));
                 if (int rc = run_iterations(d, G, st, max_iter, nllr, s, true, flags & LDPC_F_SPLIT)) return rc;
                 HIP_TRY(timed(d, LDPC_K_COUNT, s, [&] {
                     return ldpc::launch_count(G, st, d->counters + (size_t)p * LDPC_MC_NCOUNT, s);
@@ -1700,6 +1728,7 @@ int phys_mc_any(const char *fn, ldpc_decoder *d, const ldpc_graph *gp, uint64_t 
         return ldpc_fail(LDPC_EINVAL, "%s: physical graph shape %dx%d != %dx%d", fn, P.m, P.n, G.m, G.n);
     for (int p = 0; p < n_points; ++p)
         if (!(sigmas[p] > 0.0)) return ldpc_fail(LDPC_EINVAL, "%s: sigma[%d] <= 0", fn, p);
+    if (int rc = channel_frames_check(fn, d, 0)) return rc;
     DeviceGuard dg(d->g->device);
     PhysRule rule;
     if (int rc = phys_rule(fn, gp, flags, cn_rule, schedule, param, &rule)) return rc;
@@ -1732,7 +1761,7 @@ int phys_mc_any(const char *fn, ldpc_decoder *d, const ldpc_graph *gp, uint64_t 
             float *rows = (float *)d->llr_stage;  // cap x n doubles: room for cap x n floats
             HIP_TRY(timed(d, LDPC_K_GEN, s, [&] {
                 return ldpc::launch_frames(G, st, phys_tile(d), seed, p, sigmas[p], frame0 + start,
-                                           lds ? ldpc::kFramesRowLambda : ldpc::kFramesTileLambda, rows, s);
+                                           lds ? ldpc::kFramesRowLambda : ldpc::kFramesTileLambda, rows, d->chan, s);
             }));
             if (lds) {
                 HIP_TRY(timed(d, LDPC_K_PHYS, s, [&] {
@@ -2138,6 +2167,7 @@ int ldpc_phys_mc_run_q(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int
     for (int p = 0; p < n_points; ++p)
         if (!(sigmas[p] > 0.0)) return ldpc_fail(LDPC_EINVAL, "%s: sigma[%d] <= 0", fn, p);
     if (int rc = quant_check(fn, gp, flags, cn_rule, schedule, qbits, llr_scale, param_q)) return rc;
+    if (int rc = channel_frames_check(fn, d, 0)) return rc;
     DeviceGuard dg(d->g->device);
     ldpc::QuantRule rule;
     if (int rc = quant_rule(gp, flags, cn_rule, schedule, qbits, llr_scale, param_q, &rule)) return rc;
@@ -2168,7 +2198,8 @@ int ldpc_phys_mc_run_q(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int
             float *rows = (float *)d->llr_stage;
             HIP_TRY(timed(d, LDPC_K_GEN, s, [&] {
                 return ldpc::launch_frames(G, st, phys_tile(d), seed, p, sigmas[p], frame0 + start,
-                                           rule.tile ? ldpc::kFramesTileLambda : ldpc::kFramesRowLambda, rows, s);
+                                           rule.tile ? ldpc::kFramesTileLambda : ldpc::kFramesRowLambda, rows,
+                                           d->chan, s);
             }));
             if (rule.tile) {
                 if (ms.hist) HIP_TRY(ldpc::launch_mc_stats_slots(ms.slot_frame, ms.frame_base, cnt, s));
@@ -2189,6 +2220,40 @@ int ldpc_phys_mc_run_q(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int
     HIP_TRY(hipStreamSynchronize(s));
     for (int i = 0; i < need; ++i) counters_out[i] = (int64_t)h[i];
     if (d->ms_on) d->ms_state = 1;
+    return LDPC_OK;
+}
+
+// ------------------------------------------------------- channel models
+int ldpc_channel_set(ldpc_decoder *d, const ldpc_channel *ch) {
+    const char *fn = "ldpc_channel_set";
+    ldpc::FrameChannel c{};
+    if (ch) {
+        if (ch->model != LDPC_CH_REFERENCE && ch->model != LDPC_CH_AWGN && ch->model != LDPC_CH_RAYLEIGH)
+            return ldpc_fail(LDPC_EINVAL, "%s: model %d is none of LDPC_CH_REFERENCE, LDPC_CH_AWGN, LDPC_CH_RAYLEIGH", fn,
+                             ch->model);
+        if (ch->modulation != 1 && ch->modulation != 2 && ch->modulation != 4 && ch->modulation != 6)
+            return ldpc_fail(LDPC_EINVAL, "%s: modulation %d bits per symbol is none of 1 (BPSK), 2 (QPSK), 4 (16-QAM), "
+                                          "6 (64-QAM)", fn, ch->modulation);
+        if (ch->demap != LDPC_DEMAP_EXACT && ch->demap != LDPC_DEMAP_MAXLOG)
+            return ldpc_fail(LDPC_EINVAL, "%s: demap %d is neither LDPC_DEMAP_EXACT nor LDPC_DEMAP_MAXLOG", fn,
+                             ch->demap);
+        if (ch->reserved != 0) return ldpc_fail(LDPC_EINVAL, "%s: reserved must be 0, got %d", fn, ch->reserved);
+        if (ch->model == LDPC_CH_REFERENCE && ch->modulation != 1)
+            return ldpc_fail(LDPC_EINVAL, "%s: the reference channel is BPSK only (modulation 1), got %d", fn,
+                             ch->modulation);
+        c.model = ch->model;
+        c.bps = ch->modulation;
+        c.demap = ch->demap;
+    }
+    if (!d) return ldpc_fail(LDPC_EINVAL, "%s: NULL decoder", fn);
+    d->chan = c;
+    return LDPC_OK;
+}
+
+int ldpc_channel_get(const ldpc_decoder *d, ldpc_channel *out) {
+    if (!d) return ldpc_fail(LDPC_EINVAL, "ldpc_channel_get: NULL decoder");
+    if (!out) return ldpc_fail(LDPC_EINVAL, "ldpc_channel_get: NULL out");
+    *out = ldpc_channel{d->chan.model, d->chan.bps, d->chan.demap, 0};
     return LDPC_OK;
 }
 

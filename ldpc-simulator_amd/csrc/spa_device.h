@@ -286,8 +286,23 @@ enum FramesOut {
     kFramesTileLambda = 1,  // pt.Lam and pt.L, fp32 tile layout (physical tile decoder)
     kFramesRowLambda = 2,   // row_out [count][n] fp32 Lambda (physical LDS decoder)
 };
+// The channel of the frame source (include/ldpc_hip.h "channel models"; the
+// values are LDPC_CH_*, bits per symbol, LDPC_DEMAP_*).  The default is the
+// reference's mode-1 channel: frame_kernels.hip's own kernels, nothing else.
+struct FrameChannel {
+    int model = 0;
+    int bps = 1;
+    int demap = 0;
+};
 hipError_t launch_frames(const DevGraph &g, const DevState &st, const PhysTile &pt, uint64_t seed, int snr_point,
-                         double sigma, int64_t frame0, FramesOut out, float *row_out, hipStream_t s);
+                         double sigma, int64_t frame0, FramesOut out, float *row_out, const FrameChannel &ch,
+                         hipStream_t s);
+// The last stage of launch_frames under a channel model (frame_channel_models.hip;
+// ch.model != 0, g.n % ch.bps == 0): the codeword bits are in st.ubits / pt.pbits /
+// pt.wpar already.
+hipError_t launch_frame_channel_model(const DevGraph &g, const DevState &st, const PhysTile &pt, uint64_t seed,
+                                      int snr_point, double sigma, int64_t frame0, FramesOut out, float *row_out,
+                                      const FrameChannel &ch, hipStream_t s);
 // convert: L = Lambda = -(float)ch (else the generator already wrote them)
 hipError_t launch_phys_tile_init(const DevGraph &g, const DevState &st, const PhysTile &pt, bool convert,
                                  hipStream_t s);

@@ -46,7 +46,7 @@ EXPORTED = (
     "ldpc_decoder_bytes", "ldpc_decoder_create", "ldpc_decoder_destroy", "ldpc_decoder_capacity",
     "ldpc_decode_f64", "ldpc_generate_frames", "ldpc_mc_run", "ldpc_frame_order",
     "ldpc_profile_enable", "ldpc_profile_read", "ldpc_rare_rows_read", "ldpc_fixed_point_read",
-    "ldpc_mc_stats_enable", "ldpc_mc_stats_read",
+    "ldpc_mc_stats_enable", "ldpc_mc_stats_read", "ldpc_channel_set", "ldpc_channel_get",
     "ldpc_phys_lds_bytes", "ldpc_phys_decode", "ldpc_phys_mc_run",
     "ldpc_phys_decode_ex", "ldpc_phys_mc_run_ex", "ldpc_phys_kernel_name_ex", "ldpc_layers_build",
     "ldpc_phys_decode_q", "ldpc_phys_mc_run_q", "ldpc_phys_kernel_name_q", "ldpc_phys_q_lds_bytes",
@@ -72,6 +72,11 @@ P = ctypes.POINTER
 c_i32, c_i64, c_u32, c_u64, c_dbl, c_vp = (ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32,
                                            ctypes.c_uint64, ctypes.c_double, ctypes.c_void_p)
 c_flt = ctypes.c_float
+
+
+class Channel(ctypes.Structure):
+    """ldpc_channel (include/ldpc_hip.h): LDPC_CH_*, bits per symbol, LDPC_DEMAP_*, 0."""
+    _fields_ = [("model", c_i32), ("modulation", c_i32), ("demap", c_i32), ("reserved", c_i32)]
 
 
 def _declare(lib):
@@ -123,6 +128,8 @@ def _declare(lib):
         "ldpc_fixed_point_read": (ctypes.c_int, [c_vp, P(c_i64)]),
         "ldpc_mc_stats_enable": (ctypes.c_int, [c_vp, c_i32, c_i32]),
         "ldpc_mc_stats_read": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp]),
+        "ldpc_channel_set": (ctypes.c_int, [c_vp, P(Channel)]),
+        "ldpc_channel_get": (ctypes.c_int, [c_vp, P(Channel)]),
         "ldpc_comm_unique_id": (ctypes.c_int, [c_vp]),
         "ldpc_comm_init": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, P(c_vp)]),
         "ldpc_comm_allreduce": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, c_u32, c_vp]),

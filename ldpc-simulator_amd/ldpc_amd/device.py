@@ -317,6 +317,28 @@ class Decoder:
             self._h, B, dp(llr), int(max_iter), flags, dp(z), dp(conv), dp(status), dp(post), dp(nllr), dp(hist),
             dp(iters), None, ctypes.c_void_p(int(stream)) if stream else None))
 
+    def set_channel(self, spec):
+        """The frame source's channel for generate() and phys_mc_run() on this
+        decoder from now on (ldpc_channel_set): a channel.ChannelSpec, or None
+        for the reference channel.  No device work."""
+        from .channel import ChannelSpec
+        if spec is None:
+            check("ldpc_channel_set", _lib.lib().ldpc_channel_set(self._h, None))
+            return
+        if not isinstance(spec, ChannelSpec):
+            raise ValueError(f"set_channel takes a ChannelSpec or None, got {type(spec).__name__}")
+        model, bps, demap = spec.codes()
+        c = _lib.Channel(model, bps, demap, 0)
+        check("ldpc_channel_set", _lib.lib().ldpc_channel_set(self._h, ctypes.byref(c)))
+
+    @property
+    def channel(self):
+        """The channel in force, as a channel.ChannelSpec (ldpc_channel_get)."""
+        from .channel import ChannelSpec
+        c = _lib.Channel()
+        check("ldpc_channel_get", _lib.lib().ldpc_channel_get(self._h, ctypes.byref(c)))
+        return ChannelSpec.from_codes(c.model, c.modulation, c.demap)
+
     def generate(self, seed, snr_point, sigma, frame0, count, test_zero=False):
         """On-device synthetic frames (u bits, channel LLRs) copied back for testing.
         test_zero: the frame source's test-only erasures (LDPC_F_TEST_ZERO)."""

@@ -114,9 +114,11 @@ def reduce_stats(stats, snrs, world=1, allreduce=None):
     return stats
 
 
-def stats_to_json(path, seed, stats):
+def stats_to_json(path, seed, stats, channel=None):
     """Write the statistics of a sweep (reduce_stats) with its seed: the seed
-    and a point's index and failed frame indices regenerate the failed frames."""
+    and a point's index and failed frame indices regenerate the failed frames
+    (on a decoder with the same channel set).  channel: channel_info's dict of
+    the sweep, written as the document's "channel" object."""
     import json
     pts = [{"snr_db": st["snr_db"], "frames": st["frames"], "hist": [int(x) for x in st["hist"]],
             "fer_by_max_iter": [float(x) for x in st["fer_by_max_iter"]],
@@ -125,11 +127,14 @@ def stats_to_json(path, seed, stats):
             "failed": [[int(i), int(e)] for i, e in np.asarray(st["failed"]).reshape(-1, 2)],
             "failed_dropped": int(st["failed_dropped"])} for st in stats]
     with open(path, "w") as f:
-        json.dump({"seed": int(seed), "points": pts}, f, indent=1)
+        doc = {"seed": int(seed), "points": pts}
+        if channel is not None:
+            doc["channel"] = channel
+        json.dump(doc, f, indent=1)
 
 
 def run_sweep(decoder, snrs, blocks, max_iter, seed=20260213, nllr=False, speed=1.0,
-              rank=0, world=1, allreduce=None, counter_fn=None, stats_fn=None):
+              rank=0, world=1, allreduce=None, counter_fn=None, stats_fn=None, sigmas=None):
     """Counters [len(snrs), 7] for `blocks` frames per SNR point, summed over ranks.
 
     decoder     ldpc_amd.device.Decoder (its graph fixes the code) -- or None with counter_fn
@@ -139,8 +144,12 @@ def run_sweep(decoder, snrs, blocks, max_iter, seed=20260213, nllr=False, speed=
     allreduce   callable(np.ndarray int64) -> summed array (ldpc_amd.comm.Comm.allreduce)
     stats_fn    point index -> Decoder.mc_stats_read dict of the run counter_fn
                 just made; given, the result is (counters, reduce_stats(...))
+    sigmas      sigma per SNR point where the axis is not the reference's
+                (channel.sigmas_for_axis); default sigma_for_snr
     """
-    sig = [sigma_for_snr(s, speed) for s in snrs]
+    sig = [sigma_for_snr(s, speed) for s in snrs] if sigmas is None else [float(x) for x in sigmas]
+    if len(sig) != len(snrs):
+        raise ValueError(f"sigmas has {len(sig)} entries for {len(snrs)} SNR points")
     start, count = shard(int(blocks), rank, world)
     if counter_fn is None:
         def counter_fn(sigmas, cnt, frame0):
@@ -181,7 +190,7 @@ def decoder_type(cn_rule="spa", schedule="flooding", qbits=None):
 def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65536, device=0,
              rank=0, world=1, allreduce=None, matrix_path="", mode="parity", cn_rule="spa", schedule="flooding",
              alpha=0.75, beta=0.5, qbits=None, llr_scale=4.0, layered_tile=False, quant_tile=False, stats=False,
-             max_failed=0):
+             max_failed=0, channel=None, snr_axis=None):
     """Full sweep on this process's GPU -> SimulationResult (reference schema).
 
     mode "parity" is the reference's decoder on H_std; "physical" decodes the
@@ -199,7 +208,15 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
     returns (result, counters, stats): per point the Decoder.mc_stats_read dict
     (up to max_failed failed-frame records) plus snr_db, frames and
     fer_by_max_iter; with world > 1 the histograms and undetected totals are
-    summed over the ranks and max_failed must be 0."""
+    summed over the ranks and max_failed must be 0.
+    channel (a channel.ChannelSpec; None = the reference channel) puts a
+    textbook channel model under the frames; it needs mode="physical".
+    snr_axis says what `snrs` are: "reference" (the reference channel's own
+    axis, and the only one it has), "esn0" or "ebn0" (the models; Eb/N0 with the
+    code's k/n and the modulation's bits per symbol); None = "reference" for
+    the reference channel, "ebn0" for a model."""
+    snr_axis = check_channel_args(channel, snr_axis, mode)
+    from .channel import sigmas_for_axis
     from .code import EncoderDecoderData, load_committed_code
     from .device import Decoder, Graph, phys_flags, phys_quant_args, phys_rule_args
     if mode not in ("parity", "physical"):
@@ -221,15 +238,21 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
         from . import ira
         return _simulate_graph(getattr(ira, IRA_CODES[matrix])(), matrix, t0, snrs, blocks, max_iter, seed, chunk,
                                device, rank, world, allreduce, matrix_path, cn_rule, schedule, alpha, beta, qbits,
-                               llr_scale, layered_tile, quant_tile, stats, max_failed)
+                               llr_scale, layered_tile, quant_tile, stats, max_failed, channel, snr_axis)
     if isinstance(matrix, EncoderDecoderData):
         edd = matrix
     elif isinstance(matrix, str) and os.path.exists(matrix):
         edd = EncoderDecoderData(matrix)
     else:
         edd = load_committed_code(matrix)
+    sigmas = None
+    if channel is not None and not channel.is_reference:
+        channel.check_length(edd._n)  # ValueError before any device call
+        sigmas = sigmas_for_axis(channel, snr_axis, snrs, edd._k / edd._n)
     g = Graph(edd._h_std, device=device)
     dec = Decoder(g, Decoder.fit_slots(g, min(max(1, shard(int(blocks), rank, world)[1]), chunk)))
+    if sigmas is not None:
+        dec.set_channel(channel)
     counter_fn = None
     if stats:
         dec.mc_stats(True, max_failed)
@@ -242,7 +265,7 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
                                    qtile=quant_tile)
     ctr = run_sweep(dec, snrs, blocks, max_iter, seed=seed, nllr=nllr, rank=rank, world=world,
                     allreduce=allreduce, counter_fn=counter_fn,
-                    stats_fn=(lambda p: dec.mc_stats_read(p, max_iter)) if stats else None)
+                    stats_fn=(lambda p: dec.mc_stats_read(p, max_iter)) if stats else None, sigmas=sigmas)
     ctr, st = ctr if stats else (ctr, None)
     pts = point_results(ctr, edd._k, snrs, matrix_path=matrix_path or str(matrix), max_iter=max_iter)
     cfg = SimulationConfig(
@@ -253,6 +276,28 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
         threads=world, timestamp=datetime.now().isoformat())
     res = SimulationResult(config=cfg, snr_points=pts, wall_clock_seconds=time.time() - t0)
     return (res, ctr, st) if stats else (res, ctr)
+
+
+def check_channel_args(channel, snr_axis, mode):
+    """ValueError for a channel / SNR axis simulate() cannot honour (before any
+    code is loaded); returns the axis in force (channel.resolve_snr_axis)."""
+    from .channel import ChannelSpec, resolve_snr_axis
+    if channel is not None and not isinstance(channel, ChannelSpec):
+        raise ValueError(f"channel must be a ChannelSpec or None, got {type(channel).__name__}")
+    if channel is not None and not channel.is_reference and mode != "physical":
+        raise ValueError(f"the {channel.model} channel needs mode='physical' (the channel models are physical "
+                         "mode's; parity mode reproduces the reference's channel)")
+    return resolve_snr_axis(channel, snr_axis)
+
+
+def channel_info(channel, snr_axis, snrs, rate):
+    """The sweep's channel as --stats-json writes it: model, modulation, demap,
+    snr_axis and sigma per point."""
+    from .channel import ChannelSpec, resolve_snr_axis, sigmas_for_axis
+    channel = channel or ChannelSpec()
+    snr_axis = resolve_snr_axis(channel, snr_axis)
+    return {"model": channel.model, "modulation": channel.modulation, "demap": channel.demap, "snr_axis": snr_axis,
+            "sigma": [float(x) for x in sigmas_for_axis(channel, snr_axis, snrs, rate)]}
 
 
 def check_stats_args(stats, max_failed, mode, world):
@@ -269,14 +314,21 @@ def check_stats_args(stats, max_failed, mode, world):
 
 def _simulate_graph(H, name, t0, snrs, blocks, max_iter, seed, chunk, device, rank, world, allreduce, matrix_path,
                     cn_rule, schedule, alpha, beta, qbits, llr_scale, layered_tile, quant_tile=False, stats=False,
-                    max_failed=0):
+                    max_failed=0, channel=None, snr_axis="reference"):
     """simulate() in physical mode on an IRA graph H: one graph, the decoder's
     frame source and the graph it decodes on (as bench.py's config 5)."""
     from .device import Decoder, Graph
     m, n = H.shape
     k = n - m
+    sigmas = None
+    if channel is not None and not channel.is_reference:
+        from .channel import sigmas_for_axis
+        channel.check_length(n)  # ValueError before any device call
+        sigmas = sigmas_for_axis(channel, snr_axis, snrs, k / n)
     g = Graph(H, device=device)
     dec = Decoder(g, Decoder.fit_slots(g, min(max(1, shard(int(blocks), rank, world)[1]), chunk)))
+    if sigmas is not None:
+        dec.set_channel(channel)
 
     def counter_fn(sigmas, cnt, frame0):
         return dec.phys_mc_run(g, seed, sigmas, cnt, frame0, max_iter, cn=cn_rule, schedule=schedule, alpha=alpha,
@@ -284,7 +336,8 @@ def _simulate_graph(H, name, t0, snrs, blocks, max_iter, seed, chunk, device, ra
     if stats:
         dec.mc_stats(True, max_failed)
     ctr = run_sweep(dec, snrs, blocks, max_iter, seed=seed, rank=rank, world=world, allreduce=allreduce,
-                    counter_fn=counter_fn, stats_fn=(lambda p: dec.mc_stats_read(p, max_iter)) if stats else None)
+                    counter_fn=counter_fn, stats_fn=(lambda p: dec.mc_stats_read(p, max_iter)) if stats else None,
+                    sigmas=sigmas)
     ctr, st = ctr if stats else (ctr, None)
     pts = point_results(ctr, k, snrs, matrix_path=matrix_path or name, max_iter=max_iter)
     cfg = SimulationConfig(
@@ -331,15 +384,27 @@ def build_parser():
                          "FER by iteration limit, undetected errors, failed frames) to PATH")
     ap.add_argument("--max-failed", type=int, default=0, metavar="N",
                     help="with --stats-json: keep up to N failed-frame records per SNR point (default 0)")
+    ap.add_argument("--channel", choices=("reference", "awgn", "rayleigh"), default="reference",
+                    help="physical mode: a textbook channel model under the frames (default: the reference's channel)")
+    ap.add_argument("--modulation", choices=("bpsk", "qpsk", "qam16", "qam64"), default="bpsk",
+                    help="with --channel awgn / rayleigh: Gray-mapped square constellation")
+    ap.add_argument("--demap", choices=("exact", "maxlog"), default="exact",
+                    help="with --channel awgn / rayleigh: exact or max-log bit LLRs")
+    ap.add_argument("--snr-axis", choices=("reference", "esn0", "ebn0"), default=None,
+                    help="what the SNR values are: the reference channel has only 'reference'; a channel model "
+                         "takes esn0 or ebn0 (default ebn0, with the code's rate and the bits per symbol)")
     return ap
 
 
 def parse_args(argv=None):
     """Parse the command line; the physical-mode options without --mode physical,
     and combinations the decoder rejects, are argparse errors."""
+    from .channel import ChannelSpec
     from .device import phys_flags, phys_quant_args, phys_rule_args
     ap = build_parser()
     a = ap.parse_args(argv)
+    if a.channel == "reference" and (a.modulation != "bpsk" or a.demap != "exact"):
+        ap.error("--modulation and --demap need --channel awgn or rayleigh")
     if a.mode != "physical" and (a.cn_rule != "spa" or a.schedule != "flooding" or a.alpha is not None
                                  or a.beta is not None):
         ap.error("--cn-rule, --schedule, --alpha and --beta need --mode physical")
@@ -361,6 +426,8 @@ def parse_args(argv=None):
     a.alpha = 0.75 if a.alpha is None else a.alpha
     a.beta = 0.5 if a.beta is None else a.beta
     try:
+        a.channel_spec = ChannelSpec(a.channel, a.modulation, a.demap)
+        a.snr_axis = check_channel_args(a.channel_spec, a.snr_axis, a.mode)
         check_ira_mode(a.matrix, a.mode)
         phys_flags(tile=a.layered_tile, schedule=a.schedule)
         phys_rule_args(a.cn_rule, a.schedule, a.alpha, a.beta)
@@ -388,11 +455,14 @@ def main(argv=None):
                    device=local, rank=rank, world=world, allreduce=allreduce, mode=a.mode, cn_rule=a.cn_rule,
                    schedule=a.schedule, alpha=a.alpha, beta=a.beta, qbits=a.qbits, llr_scale=a.llr_scale,
                    layered_tile=a.layered_tile, quant_tile=a.quant_tile, stats=a.stats_json is not None,
-                   max_failed=a.max_failed)
+                   max_failed=a.max_failed, channel=a.channel_spec, snr_axis=a.snr_axis)
     res = out[0]
+    info = channel_info(a.channel_spec, a.snr_axis, snrs, res.config.rate)
     if rank == 0 and a.stats_json is not None:
-        stats_to_json(a.stats_json, a.seed, out[2])
+        stats_to_json(a.stats_json, a.seed, out[2], channel=info)
     if rank == 0:
+        print(f"channel {info['model']}  modulation {info['modulation']}  demap {info['demap']}  "
+              f"SNR axis {info['snr_axis']}  sigma " + " ".join(f"{x:.6f}" for x in info["sigma"]))
         for sp in res.snr_points:
             print(f"SNR {sp.snr_db:.2f} dB  FER {sp.fer:.6f}  BER {sp.ber:.6e}  "
                   f"ok {sp.successful_blocks}/{sp.total_blocks}  avg conv {sp.avg_convergence_iterations:.3f}")

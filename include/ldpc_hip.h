@@ -34,7 +34,8 @@ extern "C" {
 #define LDPC_ABI_VERSION 5  /* 5: LDPC_F_TEST_ZERO + ldpc_rare_rows_read (4: profile kinds LDPC_K_NKINDS 11);
                              * ldpc_fixed_point_read was added under 5: an addition only, nothing else changed;
                              * likewise ldpc_mc_stats_enable / ldpc_mc_stats_read and ldpc_channel_set /
-                             * ldpc_channel_get: new symbols, the version stays 5 */
+                             * ldpc_channel_get, and ldpc_rate_match_set / ldpc_rate_match_get: new symbols,
+                             * the version stays 5 */
 
 /* error codes */
 #define LDPC_OK 0
@@ -498,6 +499,63 @@ typedef struct {
 } ldpc_channel;
 int ldpc_channel_set(ldpc_decoder *d, const ldpc_channel *ch);
 int ldpc_channel_get(const ldpc_decoder *d, ldpc_channel *out);
+
+/* ------------------------------------ rate matching (physical mode only)
+ * A decoder can carry a rate-matching pattern {punctured columns, shortened
+ * columns} for the frames of ldpc_generate_frames, ldpc_phys_mc_run, _ex and
+ * _q (new symbols under ABI 5: an addition only, the version stays 5).  It is
+ * set as the channel is and is independent of it, but it belongs to the channel
+ * models: under the reference channel a pattern is LDPC_EINVAL when frames are
+ * generated.  No decoder kernel knows of it; it only changes the frames.
+ * Columns are indices in the frame's column order -- H_std order, or the IRA
+ * graph's: info 0 .. k-1, parity k .. n-1, the order ldpc_generate_frames
+ * writes.  A column is transmitted, punctured or shortened:
+ *   punctured   not sent, the receiver knows nothing; any column may be;
+ *   shortened   an information bit both ends know to be 0, not sent; only
+ *               columns j < k may be.
+ * Bits: the info words are drawn as without a pattern, then the shortened
+ * positions are cleared, before any parity is formed (for an IRA graph before
+ * the accumulator).  So the codeword is a codeword with zeros there, u_out
+ * shows the zeros, and the Monte-Carlo counters compare against them.
+ * Mapping: the transmitted columns in ascending order form the sequence
+ * t = 0 .. E-1, E = n - n_punct - n_short.  Everything the channel-model
+ * contract says of "codeword bit j" holds for transmitted position t: symbol s
+ * carries the transmitted bits s*bps .. s*bps + bps - 1 (as columns they may be
+ * far apart), takes the noise pair of counter word s and the fade of index s;
+ * BPSK bit t takes element t&1 of noise pair t>>1 and the fade of index t.  An
+ * empty pattern therefore gives the frames of no pattern, bit for bit.
+ * E % bps != 0 is LDPC_EINVAL when frames are generated; while a pattern is set
+ * this replaces the n % bps check.
+ * LLRs: a transmitted column's as under the channel model; a punctured column
+ * llr = +0.0 exactly; a shortened column llr = -LDPC_RM_KNOWN_LLR (bit 0 is
+ * known; positive means bit 1).  The decoders get Lambda = -(float)llr by the
+ * same expression as for every other column; the fixed-point decoders'
+ * quantizer saturates it to +Qmax.  Every output form (fp64 ch tiles, fp32
+ * Lam / L tiles, fp32 rows) writes every column on every launch: the buffers
+ * are reused from chunk to chunk and from pattern to pattern.
+ * Axis: sigma keeps its meaning (Es/N0 = 1 / (2 sigma^2)); Eb/N0 uses the
+ * effective rate (k - n_short) / E, which the caller applies (ldpc_amd.ratematch).
+ * Counters and statistics keep their meaning: info-bit errors are counted over
+ * all k columns, the shortened ones against 0; a failed-frame record
+ * regenerates with ldpc_generate_frames on the same decoder (same channel,
+ * same pattern).
+ * ldpc_rate_match_set validates, copies the indices into the decoder's host
+ * memory and does no device work: the device tables are uploaded by the first
+ * run that needs them, on that run's stream, and freed with the decoder.
+ * n_punct == n_short == 0 (the pointers may be NULL) clears the pattern.  It is
+ * LDPC_EINVAL, and the earlier pattern stays in force, for: a NULL decoder; a
+ * negative count; a NULL pointer with a positive count; an index outside
+ * [0, n); a duplicate within or across the two lists; a shortened index >= k;
+ * E < 1; k - n_short < 1.  LDPC_EINVAL when frames are to be generated, before
+ * any device work: a pattern under the reference channel, with
+ * LDPC_F_TEST_ZERO, in the parity-mode ldpc_mc_run and in ldpc_frame_order.
+ * ldpc_rate_match_get writes the counts and, where a list pointer is not NULL,
+ * that list in ascending order (its capacity must hold it). */
+#define LDPC_RM_KNOWN_LLR 1.0e4
+int ldpc_rate_match_set(ldpc_decoder *d, int32_t n_punct, const int32_t *punct_cols,
+                        int32_t n_short, const int32_t *short_cols);
+int ldpc_rate_match_get(const ldpc_decoder *d, int32_t *n_punct, int32_t *n_short,
+                        int32_t *punct_out, int32_t punct_cap, int32_t *short_out, int32_t short_cap);
 
 /* ------------------------------------------------ multi-GPU (RCCL, xGMI)
  * One process per GPU; frames are sharded by global index, so the only

@@ -30,6 +30,11 @@
 // Both are bound by the fp64 log / sincospi / exp of a unit, not by their
 // stores; 64 threads per block as the reference kernels, so that a small chunk
 // still spreads over the chip.
+//
+// Under a rate-matching pattern (ldpc_rate_match_set) the same two forms run as
+// frame_model_rm_kernel / frame_model_rm_row_kernel over the E transmitted bits,
+// frame_fill_kernel / frame_fill_row_kernel write the columns not sent, and
+// frame_shorten_kernel clears the shortened info bits ahead of the parity stage.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -95,9 +100,12 @@ struct Unit {
 
 // llr[0 .. kBits) of unit i of frame F; a BPSK bit past n - 1 (odd n) gets 0.
 // BPSK is one real dimension with the levels +-1: the one-bit expression with d = 1.
-template <int BPS, int MODEL, int DEMAP>
+// RM (a rate-matching pattern): n is the number of transmitted bits E and bit t
+// of the sequence is column tx[t]; else bit t is column t and tx is not read.
+template <int BPS, int MODEL, int DEMAP, bool RM = false>
 __device__ __forceinline__ void unit_llr(const uint32_t *Ut, const uint32_t *Pt, const uint32_t *Wt, int k, int n,
-                                         uint64_t seed, int64_t F, int snr_point, int i, double sigma, double *llr) {
+                                         uint64_t seed, int64_t F, int snr_point, int i, double sigma, double *llr,
+                                         const int32_t *__restrict__ tx = nullptr) {
     constexpr int M = Unit<BPS>::kAxisBits;
     constexpr int L = 1 << M;
     constexpr double d = BPS == 1   ? 1.0
@@ -128,7 +136,10 @@ __device__ __forceinline__ void unit_llr(const uint32_t *Ut, const uint32_t *Pt,
         }
         uint32_t a = 0u;  // the axis's Gray label, a_0 the most significant bit
 #pragma unroll
-        for (int t = 0; t < M; ++t) a = (a << 1) | frame_bit(Ut, Pt, Wt, k, j0 + q * M + t);
+        for (int t = 0; t < M; ++t) {
+            const int tb = j0 + q * M + t;
+            a = (a << 1) | frame_bit(Ut, Pt, Wt, k, RM ? tx[tb] : tb);
+        }
         const int B = (int)(a ^ (a >> 1) ^ (a >> 2));  // b_i = b_(i-1) xor a_i (M <= 3)
         const double x = (double)(2 * B - (L - 1)) * d;
         const double r = h[q] * x + sigma * g[q];
@@ -210,6 +221,175 @@ __global__ __launch_bounds__(64) void frame_model_row_kernel(DevGraph g, DevStat
     }
 }
 
+// ------------------------------------------------------------ rate matching
+// The two forms above under a rate-matching pattern (include/ldpc_hip.h "rate
+// matching"): instantiations of their own, so that without a pattern the
+// kernels above run exactly as they always did.  Units run over the E
+// transmitted bits; bit t of the sequence is column rm.tx_col[t] (a wave-uniform
+// load in the tile form, a per-lane gather in the row form), read from and
+// written to that column.  The columns not sent are frame_fill_*_kernel's.
+template <int BPS, int MODEL, int DEMAP>
+__global__ __launch_bounds__(64) void frame_model_rm_kernel(DevGraph g, DevState st, PhysTile pt, RateMatchDev rm,
+                                                          uint64_t seed, int snr_point, double sigma, int64_t frame0,
+                                                          int to_lambda) {
+    using U = Unit<BPS>;
+    const int kw = (g.k + 31) >> 5;
+    const int mw = (g.m + 31) >> 5;
+    const int mw32 = (mw + 31) >> 5;
+    const int units = U::count(rm.E);
+    const int per_tile = (units + U::kPerBlock - 1) / U::kPerBlock;
+    const int tile = blockIdx.x / per_tile;
+    const int i0 = (blockIdx.x % per_tile) * U::kPerBlock;
+    const int i1 = min(units, i0 + U::kPerBlock);
+    const int lane = threadIdx.x;
+    const int f = tile * kTile + lane;
+    const bool valid = f < st.count;
+    const int64_t F = frame0 + f;
+    const uint32_t *Ut = st.ubits + (size_t)tile * kw * kTile + lane;
+    const uint32_t *Pt = pt.pbits + (size_t)tile * mw * kTile + lane;
+    const uint32_t *Wt = pt.wpar + (size_t)tile * mw32 * kTile + lane;
+    double *Ct = st.ch + (size_t)tile * g.n * kTile + lane;
+    float *Lamt = pt.Lam + (size_t)tile * g.n * kTile + lane;
+    float *Lt = pt.L + (size_t)tile * g.n * kTile + lane;
+    for (int i = i0; i < i1; ++i) {
+        double llr[U::kBits];
+        unit_llr<BPS, MODEL, DEMAP, true>(Ut, Pt, Wt, g.k, rm.E, seed, F, snr_point, i, sigma, llr, rm.tx_col);
+#pragma unroll
+        for (int t = 0; t < U::kBits; ++t) {
+            const int tb = i * U::kBits + t;
+            if (tb >= rm.E) break;
+            const int j = rm.tx_col[tb];
+            const double v = valid ? llr[t] : 0.0;
+            if (to_lambda) {
+                Lamt[j * kTile] = -(float)v;
+                Lt[j * kTile] = -(float)v;
+            } else {
+                Ct[j * kTile] = v;
+            }
+        }
+    }
+}
+
+template <int BPS, int MODEL, int DEMAP>
+__global__ __launch_bounds__(64) void frame_model_rm_row_kernel(DevGraph g, DevState st, PhysTile pt, RateMatchDev rm,
+                                                              uint64_t seed, int snr_point, double sigma,
+                                                              int64_t frame0, float *__restrict__ row_out) {
+    using U = Unit<BPS>;
+    const int kw = (g.k + 31) >> 5;
+    const int mw = (g.m + 31) >> 5;
+    const int mw32 = (mw + 31) >> 5;
+    const int units = U::count(rm.E);
+    const int per_frame = (units + 63) >> 6;
+    const int f = blockIdx.x / per_frame;
+    const int i = (blockIdx.x % per_frame) * 64 + threadIdx.x;
+    if (f >= st.count || i >= units) return;
+    const int tile = f >> 6, lf = f & 63;
+    const uint32_t *Ut = st.ubits + (size_t)tile * kw * kTile + lf;
+    const uint32_t *Pt = pt.pbits + (size_t)tile * mw * kTile + lf;
+    const uint32_t *Wt = pt.wpar + (size_t)tile * mw32 * kTile + lf;
+    double llr[U::kBits];
+    unit_llr<BPS, MODEL, DEMAP, true>(Ut, Pt, Wt, g.k, rm.E, seed, frame0 + f, snr_point, i, sigma, llr, rm.tx_col);
+    float *row = row_out + (size_t)f * g.n;
+#pragma unroll
+    for (int t = 0; t < U::kBits; ++t) {
+        const int tb = i * U::kBits + t;
+        if (tb >= rm.E) break;
+        row[rm.tx_col[tb]] = -(float)llr[t];
+    }
+}
+
+// The columns a pattern does not send, tile forms: lane = frame, a block walks
+// up to 128 of them; every store is 64 consecutive frames.  The value is the
+// column's LLR (+0.0 punctured, -LDPC_RM_KNOWN_LLR shortened), through the same
+// expressions as a transmitted column's; lanes past st.count write zeros.
+constexpr int kFillPerBlock = 128;
+__global__ __launch_bounds__(64) void frame_fill_kernel(DevGraph g, DevState st, PhysTile pt, RateMatchDev rm,
+                                                      int to_lambda) {
+    const int per_tile = (rm.n_fill + kFillPerBlock - 1) / kFillPerBlock;
+    const int tile = blockIdx.x / per_tile;
+    const int c0 = (blockIdx.x % per_tile) * kFillPerBlock;
+    const int c1 = min(rm.n_fill, c0 + kFillPerBlock);
+    const int lane = threadIdx.x;
+    const bool valid = tile * kTile + lane < st.count;
+    double *Ct = st.ch + (size_t)tile * g.n * kTile + lane;
+    float *Lamt = pt.Lam + (size_t)tile * g.n * kTile + lane;
+    float *Lt = pt.L + (size_t)tile * g.n * kTile + lane;
+    for (int c = c0; c < c1; ++c) {
+        const int j = rm.fill_col[c];
+        const double v = valid ? (double)rm.fill_llr[c] : 0.0;
+        if (to_lambda) {
+            Lamt[j * kTile] = -(float)v;
+            Lt[j * kTile] = -(float)v;
+        } else {
+            Ct[j * kTile] = v;
+        }
+    }
+}
+
+// The same for the rows: one thread per (frame, column not sent).
+__global__ __launch_bounds__(64) void frame_fill_row_kernel(DevGraph g, DevState st, RateMatchDev rm,
+                                                          float *__restrict__ row_out) {
+    const int per_frame = (rm.n_fill + 63) >> 6;
+    const int f = blockIdx.x / per_frame;
+    const int c = (blockIdx.x % per_frame) * 64 + threadIdx.x;
+    if (f >= st.count || c >= rm.n_fill) return;
+    row_out[(size_t)f * g.n + rm.fill_col[c]] = -(float)(double)rm.fill_llr[c];
+}
+
+// st.ubits &= umask: lane = frame, a block takes up to 16 of the kw words.
+constexpr int kShortenWords = 16;
+__global__ __launch_bounds__(64) void frame_shorten_kernel(DevGraph g, DevState st, RateMatchDev rm) {
+    const int kw = (g.k + 31) >> 5;
+    const int per_tile = (kw + kShortenWords - 1) / kShortenWords;
+    const int tile = blockIdx.x / per_tile;
+    const int w0 = (blockIdx.x % per_tile) * kShortenWords;
+    const int w1 = min(kw, w0 + kShortenWords);
+    uint32_t *Ut = st.ubits + (size_t)tile * kw * kTile + threadIdx.x;
+    for (int w = w0; w < w1; ++w) {
+        const uint32_t mask = rm.umask[w];
+        if (mask != 0xFFFFFFFFu) Ut[w * kTile] &= mask;
+    }
+}
+
+template <int BPS, int MODEL, int DEMAP>
+hipError_t launch_model_rm(const DevGraph &g, const DevState &st, const PhysTile &pt, const RateMatchDev &rm,
+                           uint64_t seed, int snr_point, double sigma, int64_t frame0, FramesOut out, float *row_out,
+                           hipStream_t s) {
+    using U = Unit<BPS>;
+    const int units = U::count(rm.E);
+    if (out == kFramesRowLambda) {
+        frame_model_rm_row_kernel<BPS, MODEL, DEMAP><<<st.count * ((units + 63) >> 6), 64, 0, s>>>(
+            g, st, pt, rm, seed, snr_point, sigma, frame0, row_out);
+        frame_fill_row_kernel<<<st.count * ((rm.n_fill + 63) >> 6), 64, 0, s>>>(g, st, rm, row_out);
+    } else {
+        const int to_lambda = out == kFramesTileLambda ? 1 : 0;
+        frame_model_rm_kernel<BPS, MODEL, DEMAP>
+            <<<st.ntiles * ((units + U::kPerBlock - 1) / U::kPerBlock), 64, 0, s>>>(g, st, pt, rm, seed, snr_point,
+                                                                                  sigma, frame0, to_lambda);
+        frame_fill_kernel<<<st.ntiles * ((rm.n_fill + kFillPerBlock - 1) / kFillPerBlock), 64, 0, s>>>(g, st, pt, rm,
+                                                                                                    to_lambda);
+    }
+    return hipGetLastError();
+}
+
+template <int MODEL>
+hipError_t launch_model_rm_of(const DevGraph &g, const DevState &st, const PhysTile &pt, const RateMatchDev &rm,
+                              uint64_t seed, int snr_point, double sigma, int64_t frame0, FramesOut out,
+                              float *row_out, const FrameChannel &ch, hipStream_t s) {
+    const bool maxlog = ch.demap == kDemapMaxlog;
+    switch (ch.bps) {
+        case 1: return launch_model_rm<1, MODEL, 0>(g, st, pt, rm, seed, snr_point, sigma, frame0, out, row_out, s);
+        case 2: return launch_model_rm<2, MODEL, 0>(g, st, pt, rm, seed, snr_point, sigma, frame0, out, row_out, s);
+        case 4:
+            return maxlog ? launch_model_rm<4, MODEL, 1>(g, st, pt, rm, seed, snr_point, sigma, frame0, out, row_out, s)
+                          : launch_model_rm<4, MODEL, 0>(g, st, pt, rm, seed, snr_point, sigma, frame0, out, row_out, s);
+        case 6:
+            return maxlog ? launch_model_rm<6, MODEL, 1>(g, st, pt, rm, seed, snr_point, sigma, frame0, out, row_out, s)
+                          : launch_model_rm<6, MODEL, 0>(g, st, pt, rm, seed, snr_point, sigma, frame0, out, row_out, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+
 template <int BPS, int MODEL, int DEMAP>
 hipError_t launch_model(const DevGraph &g, const DevState &st, const PhysTile &pt, uint64_t seed, int snr_point,
                         double sigma, int64_t frame0, FramesOut out, float *row_out, hipStream_t s) {
@@ -254,6 +434,27 @@ hipError_t launch_frame_channel_model(const DevGraph &g, const DevState &st, con
     if (ch.model == 1)  // LDPC_CH_AWGN
         return launch_model_of<1>(g, st, pt, seed, snr_point, sigma, frame0, out, row_out, ch, s);
     return hipErrorInvalidValue;
+}
+
+hipError_t launch_frame_channel_model_rm(const DevGraph &g, const DevState &st, const PhysTile &pt, uint64_t seed,
+                                         int snr_point, double sigma, int64_t frame0, FramesOut out, float *row_out,
+                                         const FrameChannel &ch, const RateMatchDev &rm, hipStream_t s) {
+    if (ch.bps < 1 || st.count <= 0) return hipErrorInvalidValue;
+    if (rm.n_fill < 1 || rm.E < 1 || rm.E + rm.n_fill != g.n || rm.E % ch.bps != 0 || !rm.tx_col || !rm.fill_col ||
+        !rm.fill_llr)
+        return hipErrorInvalidValue;
+    if (ch.model == kChRayleigh)
+        return launch_model_rm_of<kChRayleigh>(g, st, pt, rm, seed, snr_point, sigma, frame0, out, row_out, ch, s);
+    if (ch.model == 1)  // LDPC_CH_AWGN
+        return launch_model_rm_of<1>(g, st, pt, rm, seed, snr_point, sigma, frame0, out, row_out, ch, s);
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_frame_shorten(const DevGraph &g, const DevState &st, const RateMatchDev &rm, hipStream_t s) {
+    const int kw = (g.k + 31) >> 5;
+    if (kw < 1 || !rm.umask || st.ntiles <= 0) return hipErrorInvalidValue;
+    frame_shorten_kernel<<<st.ntiles * ((kw + kShortenWords - 1) / kShortenWords), 64, 0, s>>>(g, st, rm);
+    return hipGetLastError();
 }
 
 }  // namespace ldpc

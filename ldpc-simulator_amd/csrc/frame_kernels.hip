@@ -225,7 +225,9 @@ __global__ __launch_bounds__(256) void std_parity_kernel(DevGraph g, DevState st
 
 hipError_t launch_frames(const DevGraph &g, const DevState &st, const PhysTile &pt, uint64_t seed, int snr_point,
                          double sigma, int64_t frame0, FramesOut out, float *row_out, const FrameChannel &ch,
-                         hipStream_t s) {
+                         hipStream_t s, const RateMatchDev &rm) {
+    // a rate-matching pattern belongs to the channel models (the API refuses it under the reference channel)
+    if (rm.n_fill > 0 && ch.model == 0) return hipErrorInvalidValue;
     const int kw = (g.k + 31) >> 5, mw = (g.m + 31) >> 5;
     const int nblk = (kw + 3) >> 2, bpb = 16;
     const int nbc = (nblk + bpb - 1) / bpb;
@@ -233,6 +235,8 @@ hipError_t launch_frames(const DevGraph &g, const DevState &st, const PhysTile &
     hipError_t e = hipMemsetAsync(pt.wpar, 0, sizeof(uint32_t) * (size_t)st.ntiles * mw32 * kTile, s);
     if (e != hipSuccess) return e;
     if (g.k > 0) frame_ubits_kernel<<<st.ntiles * nbc, 64, 0, s>>>(g, st, seed, snr_point, frame0, bpb);
+    // shortened info bits are zeros before any parity is formed: the codeword is a codeword with zeros there
+    if (rm.n_short > 0 && (e = launch_frame_shorten(g, st, rm, s)) != hipSuccess) return e;
     if (g.ira) {
         ira_sbits_kernel<<<st.ntiles * ((mw + 3) >> 2), 256, 0, s>>>(g, st, pt, g.row_ptr, g.col_idx);
         ira_carry_kernel<<<st.ntiles, 64, 0, s>>>(g, pt);
@@ -246,6 +250,8 @@ hipError_t launch_frames(const DevGraph &g, const DevState &st, const PhysTile &
             std_parity_kernel<0><<<grid, 256, 0, s>>>(g, st, pt, g.a_packed);
     }
     // a channel model (physical mode only): the same bits, its own last stage
+    if (rm.n_fill > 0)
+        return launch_frame_channel_model_rm(g, st, pt, seed, snr_point, sigma, frame0, out, row_out, ch, rm, s);
     if (ch.model != 0) return launch_frame_channel_model(g, st, pt, seed, snr_point, sigma, frame0, out, row_out, ch, s);
     const int npairs = (g.n + 1) >> 1;
     if (out == kFramesRowLambda)

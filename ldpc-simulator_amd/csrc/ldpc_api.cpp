@@ -18,6 +18,7 @@
 
 #include "ldpc_internal.h"
 #include "mc_stats_host.h"
+#include "rate_match_host.h"
 #include "spa_device.h"
 
 using ldpc::DevGraph;
@@ -120,6 +121,12 @@ struct ldpc_decoder {
     int ms_points = 0, ms_T = 0, ms_run_failed = 0;  // of the run in ms_buf
     // the frame source's channel (ldpc_channel_set); the default is the reference's
     ldpc::FrameChannel chan{};
+    // the frame source's rate-matching pattern (ldpc_rate_match_set): the lists on the host; the kernels'
+    // tables (rate_match_host.h) go to rm_dev on the first run that needs them, on that run's stream
+    std::vector<int32_t> rm_punct, rm_short;
+    ldpc::RateMatchTables rm_tab;  // what rm_dev holds (or is about to)
+    uint32_t *rm_dev = nullptr;    // rate_match_max_words(n, k) words, allocated once
+    bool rm_stale = false;         // the pattern changed since rm_dev was written
     // profiling (ldpc_profile_*)
     bool prof = false;
     struct Span {
@@ -299,9 +306,17 @@ DevGraph call_graph(const ldpc_decoder *d, uint32_t flags) {
 // hold (no device work): the code length divides into symbols, and the
 // test-only erasures belong to the reference channel.
 int channel_frames_check(const char *fn, const ldpc_decoder *d, uint32_t flags) {
+    const int n_fill = (int)(d->rm_punct.size() + d->rm_short.size());
+    if (n_fill > 0 && d->chan.model == LDPC_CH_REFERENCE)
+        return ldpc_fail(LDPC_EINVAL, "%s: a rate-matching pattern (ldpc_rate_match_set) needs a channel model, this "
+                                      "decoder has the reference channel (ldpc_channel_set)", fn);
     if (d->chan.model == LDPC_CH_REFERENCE) return LDPC_OK;
     const int n = d->g->dg.n;
-    if (n % d->chan.bps != 0)
+    if (n_fill > 0 && (n - n_fill) % d->chan.bps != 0)
+        return ldpc_fail(LDPC_EINVAL, "%s: E = %d transmitted bits (n = %d less %d punctured and %d shortened) is not a "
+                                      "multiple of bps = %d (the channel's bits per symbol)", fn, n - n_fill, n,
+                         (int)d->rm_punct.size(), (int)d->rm_short.size(), d->chan.bps);
+    if (n_fill == 0 && n % d->chan.bps != 0)
         return ldpc_fail(LDPC_EINVAL, "%s: n = %d is not a multiple of bps = %d (the channel's bits per symbol)", fn, n,
                          d->chan.bps);
     if (flags & LDPC_F_TEST_ZERO)
@@ -312,9 +327,41 @@ int channel_frames_check(const char *fn, const ldpc_decoder *d, uint32_t flags) 
 
 // The parity-mode entries reproduce the reference: its channel only.
 int channel_parity_check(const char *fn, const ldpc_decoder *d) {
+    if (!d->rm_punct.empty() || !d->rm_short.empty())
+        return ldpc_fail(LDPC_EINVAL, "%s: parity mode sends every code whole; rate matching is physical mode's "
+                                      "(ldpc_rate_match_set(d, 0, NULL, 0, NULL) clears the pattern)", fn);
     if (d->chan.model == LDPC_CH_REFERENCE) return LDPC_OK;
     return ldpc_fail(LDPC_EINVAL, "%s: parity mode has the reference channel only; the channel models are physical "
                                   "mode's (ldpc_channel_set(d, NULL) puts the reference channel back)", fn);
+}
+
+// The decoder's rate-matching pattern for the frame source's kernels: nothing
+// (n_fill = 0) without one, else its tables in device memory, uploaded on
+// stream s if the pattern changed since they were (a copy from pageable host
+// memory: rm_tab has been read when hipMemcpyAsync returns).
+int rate_match_dev(ldpc_decoder *d, hipStream_t s, ldpc::RateMatchDev *out) {
+    *out = ldpc::RateMatchDev{};
+    if (d->rm_punct.empty() && d->rm_short.empty()) return LDPC_OK;
+    const DevGraph &G = d->g->dg;
+    if (!d->rm_dev) {
+        if (int rc = dev_alloc(&d->rm_dev, ldpc::rate_match_max_words(G.n, G.k))) return rc;
+        d->rm_stale = true;
+    }
+    if (d->rm_stale) {
+        d->rm_tab = ldpc::rate_match_build(G.n, G.k, d->rm_punct, d->rm_short);
+        HIP_TRY(hipMemcpyAsync(d->rm_dev, d->rm_tab.words.data(), sizeof(uint32_t) * d->rm_tab.words.size(),
+                               hipMemcpyHostToDevice, s));
+        d->rm_stale = false;
+    }
+    const ldpc::RateMatchTables &t = d->rm_tab;
+    out->tx_col = reinterpret_cast<const int32_t *>(d->rm_dev + t.tx_off());
+    out->fill_col = reinterpret_cast<const int32_t *>(d->rm_dev + t.fill_off());
+    out->fill_llr = reinterpret_cast<const float *>(d->rm_dev + t.llr_off());
+    out->umask = d->rm_dev + t.mask_off();
+    out->E = t.E;
+    out->n_fill = t.n_fill;
+    out->n_short = (int)d->rm_short.size();
+    return LDPC_OK;
 }
 
 hipEvent_t take_event(ldpc_decoder *d) {
@@ -830,6 +877,7 @@ int ldpc_decoder_destroy(ldpc_decoder *d) {
     (void)hipFree(d->ms_buf);
     (void)hipFree(d->ms_slots);
     (void)hipFree(d->ms_tile);
+    (void)hipFree(d->rm_dev);
     for (auto &sp : d->spans) {
         (void)hipEventDestroy(sp.a);
         (void)hipEventDestroy(sp.b);
@@ -1001,12 +1049,13 @@ int ldpc_generate_frames(ldpc_decoder *d, uint64_t seed, int32_t snr_point, doub
         u_dev = u_out;
         l_dev = llr_out;
     }
-    if ((rc = ensure_pbits(d, G))) {
+    ldpc::RateMatchDev rm;
+    if ((rc = ensure_pbits(d, G)) || (rc = rate_match_dev(d, s, &rm))) {
         (void)hipFree(dev_ptrs ? nullptr : u_dev);
         return rc;
     }
     HIP_TRY(ldpc::launch_frames(G, d->st, phys_tile(d), seed, snr_point, sigma, frame0, ldpc::kFramesCh, nullptr,
-                                d->chan, s));
+                                d->chan, s, rm));
     // export writes u only for j<k, at [f][k]: give it the [count][k] buffer
     HIP_TRY(ldpc::launch_export_frames(G, d->st, u_dev, l_dev, s));
     if (!dev_ptrs) {
@@ -1737,6 +1786,8 @@ int phys_mc_any(const char *fn, ldpc_decoder *d, const ldpc_graph *gp, uint64_t 
     if (!lds)
         if (int rc = ensure_phys_tile(d, P)) return rc;
     if (int rc = ensure_pbits(d, G)) return rc;
+    ldpc::RateMatchDev rm;
+    if (int rc = rate_match_dev(d, s, &rm)) return rc;
     const int need = n_points * LDPC_MC_NCOUNT;
     if (d->counters_cap < need) {
         (void)hipFree(d->counters);
@@ -1761,7 +1812,8 @@ int phys_mc_any(const char *fn, ldpc_decoder *d, const ldpc_graph *gp, uint64_t 
             float *rows = (float *)d->llr_stage;  // cap x n doubles: room for cap x n floats
             HIP_TRY(timed(d, LDPC_K_GEN, s, [&] {
                 return ldpc::launch_frames(G, st, phys_tile(d), seed, p, sigmas[p], frame0 + start,
-                                           lds ? ldpc::kFramesRowLambda : ldpc::kFramesTileLambda, rows, d->chan, s);
+                                           lds ? ldpc::kFramesRowLambda : ldpc::kFramesTileLambda, rows, d->chan, s,
+                                           rm);
             }));
             if (lds) {
                 HIP_TRY(timed(d, LDPC_K_PHYS, s, [&] {
@@ -2175,6 +2227,8 @@ int ldpc_phys_mc_run_q(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int
     if (rule.tile)
         if (int rc = ensure_phys_tile(d, P)) return rc;
     if (int rc = ensure_pbits(d, G)) return rc;
+    ldpc::RateMatchDev rm;
+    if (int rc = rate_match_dev(d, s, &rm)) return rc;
     const int need = n_points * LDPC_MC_NCOUNT;
     if (d->counters_cap < need) {
         (void)hipFree(d->counters);
@@ -2199,7 +2253,7 @@ int ldpc_phys_mc_run_q(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int
             HIP_TRY(timed(d, LDPC_K_GEN, s, [&] {
                 return ldpc::launch_frames(G, st, phys_tile(d), seed, p, sigmas[p], frame0 + start,
                                            rule.tile ? ldpc::kFramesTileLambda : ldpc::kFramesRowLambda, rows,
-                                           d->chan, s);
+                                           d->chan, s, rm);
             }));
             if (rule.tile) {
                 if (ms.hist) HIP_TRY(ldpc::launch_mc_stats_slots(ms.slot_frame, ms.frame_base, cnt, s));
@@ -2254,6 +2308,41 @@ int ldpc_channel_get(const ldpc_decoder *d, ldpc_channel *out) {
     if (!d) return ldpc_fail(LDPC_EINVAL, "ldpc_channel_get: NULL decoder");
     if (!out) return ldpc_fail(LDPC_EINVAL, "ldpc_channel_get: NULL out");
     *out = ldpc_channel{d->chan.model, d->chan.bps, d->chan.demap, 0};
+    return LDPC_OK;
+}
+
+// ------------------------------------------------------- rate matching
+int ldpc_rate_match_set(ldpc_decoder *d, int32_t n_punct, const int32_t *punct_cols, int32_t n_short,
+                        const int32_t *short_cols) {
+    const char *fn = "ldpc_rate_match_set";
+    if (!d) return ldpc_fail(LDPC_EINVAL, "%s: NULL decoder", fn);
+    const DevGraph &G = d->g->dg;
+    const std::string err = ldpc::rate_match_validate(G.n, G.k, n_punct, punct_cols, n_short, short_cols);
+    if (!err.empty()) return ldpc_fail(LDPC_EINVAL, "%s: %s", fn, err.c_str());
+    d->rm_punct.assign(punct_cols, punct_cols + n_punct);
+    d->rm_short.assign(short_cols, short_cols + n_short);
+    std::sort(d->rm_punct.begin(), d->rm_punct.end());
+    std::sort(d->rm_short.begin(), d->rm_short.end());
+    d->rm_stale = true;
+    return LDPC_OK;
+}
+
+int ldpc_rate_match_get(const ldpc_decoder *d, int32_t *n_punct, int32_t *n_short, int32_t *punct_out,
+                        int32_t punct_cap, int32_t *short_out, int32_t short_cap) {
+    const char *fn = "ldpc_rate_match_get";
+    if (!d) return ldpc_fail(LDPC_EINVAL, "%s: NULL decoder", fn);
+    if (!n_punct || !n_short || punct_cap < 0 || short_cap < 0 || (punct_cap > 0 && !punct_out) ||
+        (short_cap > 0 && !short_out))
+        return ldpc_fail(LDPC_EINVAL, "%s: bad arguments", fn);
+    *n_punct = (int32_t)d->rm_punct.size();
+    *n_short = (int32_t)d->rm_short.size();
+    if (punct_out || short_out) {
+        if ((punct_out && punct_cap < *n_punct) || (short_out && short_cap < *n_short))
+            return ldpc_fail(LDPC_EINVAL, "%s: capacities %d / %d are too small for %d punctured and %d shortened "
+                                          "columns", fn, punct_cap, short_cap, *n_punct, *n_short);
+        if (punct_out) std::copy(d->rm_punct.begin(), d->rm_punct.end(), punct_out);
+        if (short_out) std::copy(d->rm_short.begin(), d->rm_short.end(), short_out);
+    }
     return LDPC_OK;
 }
 

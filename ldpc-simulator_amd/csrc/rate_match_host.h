@@ -1,0 +1,92 @@
+// rate_match_host.h -- host side of the frame source's rate-matching pattern
+// (include/ldpc_hip.h "rate matching"): the validation of ldpc_rate_match_set
+// and the tables the kernels of frame_rate_match.hip read.  No HIP here, so a
+// stand-alone program can run it under a sanitizer
+// (tools/rate_match_host_check.cpp).
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace ldpc {
+
+constexpr float kRateMatchKnownLlr = 1.0e4f;  // LDPC_RM_KNOWN_LLR: exact in fp32 and fp64
+
+// Empty when {punct, shrt} is a pattern a code with n columns, k of them
+// information columns, can carry; else what is wrong with it (the contract's
+// list, in its order).
+inline std::string rate_match_validate(int n, int k, int32_t n_punct, const int32_t *punct, int32_t n_short,
+                                       const int32_t *shrt) {
+    if (n_punct < 0 || n_short < 0)
+        return "negative count (n_punct = " + std::to_string(n_punct) + ", n_short = " + std::to_string(n_short) + ")";
+    if ((n_punct > 0 && !punct) || (n_short > 0 && !shrt)) return "NULL column list with a positive count";
+    if (n_punct > n || n_short > n) return "more columns listed than the code has (n = " + std::to_string(n) + ")";
+    std::vector<uint8_t> seen((size_t)std::max(n, 0), 0);
+    for (int pass = 0; pass < 2; ++pass) {
+        const int32_t *cols = pass ? shrt : punct;
+        const int32_t cnt = pass ? n_short : n_punct;
+        const char *what = pass ? "shortened" : "punctured";
+        for (int32_t i = 0; i < cnt; ++i) {
+            const int32_t c = cols[i];
+            if (c < 0 || c >= n)
+                return std::string(what) + " column " + std::to_string(c) + " is outside [0, " + std::to_string(n) + ")";
+            if (seen[(size_t)c]) return std::string("column ") + std::to_string(c) + " is listed twice (duplicate)";
+            seen[(size_t)c] = 1;
+        }
+    }
+    for (int32_t i = 0; i < n_short; ++i)
+        if (shrt[i] >= k)
+            return "shortened column " + std::to_string(shrt[i]) + " is not an information column (k = " +
+                   std::to_string(k) + ")";
+    if (n - n_punct - n_short < 1) return "no transmitted column is left (E < 1)";
+    if (k - n_short < 1) return "no information bit is left (k - n_short < 1)";
+    return std::string();
+}
+
+// What the kernels read, as one block of 32-bit words: tx_col [E] (the
+// transmitted columns, ascending), fill_col [n_fill] (the others, ascending),
+// fill_llr [n_fill] (fp32: +0.0 punctured, -kRateMatchKnownLlr shortened),
+// umask [kw] (bit j%32 of word j/32 clear for a shortened column j).
+struct RateMatchTables {
+    int E = 0, n_fill = 0, kw = 0;
+    std::vector<uint32_t> words;
+    size_t tx_off() const { return 0; }
+    size_t fill_off() const { return (size_t)E; }
+    size_t llr_off() const { return (size_t)E + (size_t)n_fill; }
+    size_t mask_off() const { return (size_t)E + 2 * (size_t)n_fill; }
+};
+
+// Words the tables of any pattern of an (n, k) code fit in.
+inline size_t rate_match_max_words(int n, int k) { return 2 * (size_t)n + (size_t)((k + 31) >> 5); }
+
+// The tables of a validated pattern.
+inline RateMatchTables rate_match_build(int n, int k, const std::vector<int32_t> &punct,
+                                        const std::vector<int32_t> &shrt) {
+    std::vector<uint8_t> kind((size_t)n, 0);  // 0 transmitted, 1 punctured, 2 shortened
+    for (int32_t c : punct) kind[(size_t)c] = 1;
+    for (int32_t c : shrt) kind[(size_t)c] = 2;
+    RateMatchTables t;
+    t.n_fill = (int)(punct.size() + shrt.size());
+    t.E = n - t.n_fill;
+    t.kw = (k + 31) >> 5;
+    t.words.assign(t.mask_off() + (size_t)t.kw, 0u);
+    size_t it = t.tx_off(), jf = 0;
+    for (int j = 0; j < n; ++j) {
+        if (kind[(size_t)j] == 0) {
+            t.words[it++] = (uint32_t)j;
+            continue;
+        }
+        const float v = kind[(size_t)j] == 2 ? -kRateMatchKnownLlr : 0.0f;
+        t.words[t.fill_off() + jf] = (uint32_t)j;
+        std::memcpy(&t.words[t.llr_off() + jf], &v, sizeof v);
+        ++jf;
+    }
+    for (int w = 0; w < t.kw; ++w) t.words[t.mask_off() + (size_t)w] = 0xFFFFFFFFu;
+    for (int32_t c : shrt) t.words[t.mask_off() + (size_t)(c >> 5)] &= ~(1u << (c & 31));
+    return t;
+}
+
+}  // namespace ldpc

@@ -294,15 +294,33 @@ struct FrameChannel {
     int bps = 1;
     int demap = 0;
 };
+// A decoder's rate-matching pattern as the frame source's kernels read it
+// (include/ldpc_hip.h "rate matching"; tables built by rate_match_host.h, in
+// device memory the decoder owns).  Per decoder, so not in DevGraph: a graph is
+// shared.  The default (n_fill == 0) is no pattern: every column is sent.
+struct RateMatchDev {
+    const int32_t *tx_col = nullptr;    // [E] transmitted columns, ascending
+    const int32_t *fill_col = nullptr;  // [n_fill] the columns not sent
+    const float *fill_llr = nullptr;    // [n_fill] their LLR: +0.0 punctured, -LDPC_RM_KNOWN_LLR shortened
+    const uint32_t *umask = nullptr;    // [kw] AND mask of st.ubits (shortened bits clear)
+    int E = 0, n_fill = 0, n_short = 0;
+};
 hipError_t launch_frames(const DevGraph &g, const DevState &st, const PhysTile &pt, uint64_t seed, int snr_point,
                          double sigma, int64_t frame0, FramesOut out, float *row_out, const FrameChannel &ch,
-                         hipStream_t s);
+                         hipStream_t s, const RateMatchDev &rm = RateMatchDev{});
 // The last stage of launch_frames under a channel model (frame_channel_models.hip;
 // ch.model != 0, g.n % ch.bps == 0): the codeword bits are in st.ubits / pt.pbits /
 // pt.wpar already.
 hipError_t launch_frame_channel_model(const DevGraph &g, const DevState &st, const PhysTile &pt, uint64_t seed,
                                       int snr_point, double sigma, int64_t frame0, FramesOut out, float *row_out,
                                       const FrameChannel &ch, hipStream_t s);
+// The same under a rate-matching pattern (rm.n_fill > 0, rm.E % ch.bps == 0):
+// the transmitted columns' LLRs, then the fill of the others.
+hipError_t launch_frame_channel_model_rm(const DevGraph &g, const DevState &st, const PhysTile &pt, uint64_t seed,
+                                         int snr_point, double sigma, int64_t frame0, FramesOut out, float *row_out,
+                                         const FrameChannel &ch, const RateMatchDev &rm, hipStream_t s);
+// st.ubits &= rm.umask, between the info words and the parity stage (rm.n_short > 0)
+hipError_t launch_frame_shorten(const DevGraph &g, const DevState &st, const RateMatchDev &rm, hipStream_t s);
 // convert: L = Lambda = -(float)ch (else the generator already wrote them)
 hipError_t launch_phys_tile_init(const DevGraph &g, const DevState &st, const PhysTile &pt, bool convert,
                                  hipStream_t s);

@@ -339,6 +339,33 @@ class Decoder:
         check("ldpc_channel_get", _lib.lib().ldpc_channel_get(self._h, ctypes.byref(c)))
         return ChannelSpec.from_codes(c.model, c.modulation, c.demap)
 
+    def set_rate_match(self, rm):
+        """The frame source's rate-matching pattern for generate() and
+        phys_mc_run() on this decoder from now on (ldpc_rate_match_set): a
+        ratematch.RateMatch; None or an empty one clears it.  Validated here
+        (ValueError) and by the library; no device work."""
+        from .ratematch import RateMatch
+        if rm is None:
+            rm = RateMatch()
+        if not isinstance(rm, RateMatch):
+            raise ValueError(f"set_rate_match takes a RateMatch or None, got {type(rm).__name__}")
+        rm.validate(self.graph.n, self.graph.k)
+        p, s = _lib.as_i32(rm.punctured), _lib.as_i32(rm.shortened)
+        check("ldpc_rate_match_set", _lib.lib().ldpc_rate_match_set(
+            self._h, len(p), _lib.i32p(p) if len(p) else None, len(s), _lib.i32p(s) if len(s) else None))
+
+    @property
+    def rate_match(self):
+        """The pattern in force, as a ratematch.RateMatch (ldpc_rate_match_get)."""
+        from .ratematch import RateMatch
+        npu, nsh = _lib.c_i32(), _lib.c_i32()
+        check("ldpc_rate_match_get", _lib.lib().ldpc_rate_match_get(
+            self._h, ctypes.byref(npu), ctypes.byref(nsh), None, 0, None, 0))
+        p, s = np.zeros(max(npu.value, 1), np.int32), np.zeros(max(nsh.value, 1), np.int32)
+        check("ldpc_rate_match_get", _lib.lib().ldpc_rate_match_get(
+            self._h, ctypes.byref(npu), ctypes.byref(nsh), _lib.i32p(p), len(p), _lib.i32p(s), len(s)))
+        return RateMatch(tuple(int(x) for x in p[:npu.value]), tuple(int(x) for x in s[:nsh.value]))
+
     def generate(self, seed, snr_point, sigma, frame0, count, test_zero=False):
         """On-device synthetic frames (u bits, channel LLRs) copied back for testing.
         test_zero: the frame source's test-only erasures (LDPC_F_TEST_ZERO)."""

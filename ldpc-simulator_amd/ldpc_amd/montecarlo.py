@@ -190,7 +190,7 @@ def decoder_type(cn_rule="spa", schedule="flooding", qbits=None):
 def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65536, device=0,
              rank=0, world=1, allreduce=None, matrix_path="", mode="parity", cn_rule="spa", schedule="flooding",
              alpha=0.75, beta=0.5, qbits=None, llr_scale=4.0, layered_tile=False, quant_tile=False, stats=False,
-             max_failed=0, channel=None, snr_axis=None):
+             max_failed=0, channel=None, snr_axis=None, rate_match=None):
     """Full sweep on this process's GPU -> SimulationResult (reference schema).
 
     mode "parity" is the reference's decoder on H_std; "physical" decodes the
@@ -214,8 +214,14 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
     snr_axis says what `snrs` are: "reference" (the reference channel's own
     axis, and the only one it has), "esn0" or "ebn0" (the models; Eb/N0 with the
     code's k/n and the modulation's bits per symbol); None = "reference" for
-    the reference channel, "ebn0" for a model."""
+    the reference channel, "ebn0" for a model.
+    rate_match (a ratematch.RateMatch; None = every column is sent) punctures
+    and shortens the frames; it needs mode="physical" and a channel model.  The
+    Eb/N0 axis and the config's rate then use the effective rate
+    (k - n_short) / E, the BER counts k - n_short information bits, and the
+    config's n, m, k stay the mother code's."""
     snr_axis = check_channel_args(channel, snr_axis, mode)
+    rate_match = check_rate_match_args(rate_match, channel, mode)
     from .channel import sigmas_for_axis
     from .code import EncoderDecoderData, load_committed_code
     from .device import Decoder, Graph, phys_flags, phys_quant_args, phys_rule_args
@@ -238,7 +244,7 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
         from . import ira
         return _simulate_graph(getattr(ira, IRA_CODES[matrix])(), matrix, t0, snrs, blocks, max_iter, seed, chunk,
                                device, rank, world, allreduce, matrix_path, cn_rule, schedule, alpha, beta, qbits,
-                               llr_scale, layered_tile, quant_tile, stats, max_failed, channel, snr_axis)
+                               llr_scale, layered_tile, quant_tile, stats, max_failed, channel, snr_axis, rate_match)
     if isinstance(matrix, EncoderDecoderData):
         edd = matrix
     elif isinstance(matrix, str) and os.path.exists(matrix):
@@ -246,13 +252,17 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
     else:
         edd = load_committed_code(matrix)
     sigmas = None
+    rate, k_info = edd._rate, edd._k
     if channel is not None and not channel.is_reference:
-        channel.check_length(edd._n)  # ValueError before any device call
-        sigmas = sigmas_for_axis(channel, snr_axis, snrs, edd._k / edd._n)
+        # ValueErrors before any device call
+        sent, k_info, rate = rate_match_shape(rate_match, channel, edd._n, edd._k)
+        channel.check_length(sent)
+        sigmas = sigmas_for_axis(channel, snr_axis, snrs, rate)
     g = Graph(edd._h_std, device=device)
     dec = Decoder(g, Decoder.fit_slots(g, min(max(1, shard(int(blocks), rank, world)[1]), chunk)))
     if sigmas is not None:
         dec.set_channel(channel)
+        dec.set_rate_match(rate_match)
     counter_fn = None
     if stats:
         dec.mc_stats(True, max_failed)
@@ -267,9 +277,9 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
                     allreduce=allreduce, counter_fn=counter_fn,
                     stats_fn=(lambda p: dec.mc_stats_read(p, max_iter)) if stats else None, sigmas=sigmas)
     ctr, st = ctr if stats else (ctr, None)
-    pts = point_results(ctr, edd._k, snrs, matrix_path=matrix_path or str(matrix), max_iter=max_iter)
+    pts = point_results(ctr, k_info, snrs, matrix_path=matrix_path or str(matrix), max_iter=max_iter)
     cfg = SimulationConfig(
-        matrix_path=matrix_path or str(matrix), n=edd._n, m=edd._m, k=edd._k, rate=edd._rate,
+        matrix_path=matrix_path or str(matrix), n=edd._n, m=edd._m, k=edd._k, rate=rate,
         blocks=int(blocks), max_iterations=int(max_iter), encoding_method="standard",
         interleaver_type="none", decoder_type=decoder_type(cn_rule, schedule, qbits), channel_mode=1, modulation=1,
         speed=1.0, snr_range=(snrs[0], snrs[-1], (snrs[1] - snrs[0]) if len(snrs) > 1 else 0.0),
@@ -290,14 +300,47 @@ def check_channel_args(channel, snr_axis, mode):
     return resolve_snr_axis(channel, snr_axis)
 
 
-def channel_info(channel, snr_axis, snrs, rate):
+def check_rate_match_args(rate_match, channel, mode):
+    """ValueError for a rate-matching pattern simulate() cannot honour (before
+    any code is loaded); returns the pattern, None for an empty one."""
+    from .ratematch import RateMatch
+    if rate_match is None:
+        return None
+    if not isinstance(rate_match, RateMatch):
+        raise ValueError(f"rate_match must be a RateMatch or None, got {type(rate_match).__name__}")
+    if rate_match.is_empty:
+        return None
+    if mode != "physical":
+        raise ValueError("rate_match needs mode='physical' (parity mode sends every code whole)")
+    if channel is None or channel.is_reference:
+        raise ValueError("rate_match needs a channel model (channel=ChannelSpec('awgn' / 'rayleigh', ...)): the "
+                         "reference channel sends every code whole")
+    return rate_match
+
+
+def rate_match_shape(rate_match, channel, n, k):
+    """(transmitted bits E, information bits, effective rate) of an (n, k) code
+    under the pattern (None: n, k, k / n); ValueError for a pattern the code or
+    the channel's bits per symbol cannot carry."""
+    if rate_match is None or rate_match.is_empty:
+        return int(n), int(k), k / n
+    rate_match.validate(n, k, channel.bps)
+    return rate_match.n_transmitted(n), rate_match.info_bits(k), rate_match.effective_rate(n, k)
+
+
+def channel_info(channel, snr_axis, snrs, rate, rate_match=None, n=None, k=None):
     """The sweep's channel as --stats-json writes it: model, modulation, demap,
-    snr_axis and sigma per point."""
+    snr_axis and sigma per point; under a rate-matching pattern (then with the
+    mother code's n and k, and `rate` the effective rate) also "rate_match":
+    the columns, the transmitted and information bits and the rate."""
     from .channel import ChannelSpec, resolve_snr_axis, sigmas_for_axis
     channel = channel or ChannelSpec()
     snr_axis = resolve_snr_axis(channel, snr_axis)
-    return {"model": channel.model, "modulation": channel.modulation, "demap": channel.demap, "snr_axis": snr_axis,
+    info = {"model": channel.model, "modulation": channel.modulation, "demap": channel.demap, "snr_axis": snr_axis,
             "sigma": [float(x) for x in sigmas_for_axis(channel, snr_axis, snrs, rate)]}
+    if rate_match is not None and not rate_match.is_empty:
+        info["rate_match"] = rate_match.info(n, k)
+    return info
 
 
 def check_stats_args(stats, max_failed, mode, world):
@@ -314,21 +357,25 @@ def check_stats_args(stats, max_failed, mode, world):
 
 def _simulate_graph(H, name, t0, snrs, blocks, max_iter, seed, chunk, device, rank, world, allreduce, matrix_path,
                     cn_rule, schedule, alpha, beta, qbits, llr_scale, layered_tile, quant_tile=False, stats=False,
-                    max_failed=0, channel=None, snr_axis="reference"):
+                    max_failed=0, channel=None, snr_axis="reference", rate_match=None):
     """simulate() in physical mode on an IRA graph H: one graph, the decoder's
     frame source and the graph it decodes on (as bench.py's config 5)."""
     from .device import Decoder, Graph
     m, n = H.shape
     k = n - m
     sigmas = None
+    rate, k_info = k / n, k
     if channel is not None and not channel.is_reference:
         from .channel import sigmas_for_axis
-        channel.check_length(n)  # ValueError before any device call
-        sigmas = sigmas_for_axis(channel, snr_axis, snrs, k / n)
+        # ValueErrors before any device call
+        sent, k_info, rate = rate_match_shape(rate_match, channel, n, k)
+        channel.check_length(sent)
+        sigmas = sigmas_for_axis(channel, snr_axis, snrs, rate)
     g = Graph(H, device=device)
     dec = Decoder(g, Decoder.fit_slots(g, min(max(1, shard(int(blocks), rank, world)[1]), chunk)))
     if sigmas is not None:
         dec.set_channel(channel)
+        dec.set_rate_match(rate_match)
 
     def counter_fn(sigmas, cnt, frame0):
         return dec.phys_mc_run(g, seed, sigmas, cnt, frame0, max_iter, cn=cn_rule, schedule=schedule, alpha=alpha,
@@ -339,9 +386,9 @@ def _simulate_graph(H, name, t0, snrs, blocks, max_iter, seed, chunk, device, ra
                     counter_fn=counter_fn, stats_fn=(lambda p: dec.mc_stats_read(p, max_iter)) if stats else None,
                     sigmas=sigmas)
     ctr, st = ctr if stats else (ctr, None)
-    pts = point_results(ctr, k, snrs, matrix_path=matrix_path or name, max_iter=max_iter)
+    pts = point_results(ctr, k_info, snrs, matrix_path=matrix_path or name, max_iter=max_iter)
     cfg = SimulationConfig(
-        matrix_path=matrix_path or name, n=n, m=m, k=k, rate=k / n, blocks=int(blocks),
+        matrix_path=matrix_path or name, n=n, m=m, k=k, rate=rate, blocks=int(blocks),
         max_iterations=int(max_iter), encoding_method="standard", interleaver_type="none",
         decoder_type=decoder_type(cn_rule, schedule, qbits), channel_mode=1, modulation=1, speed=1.0,
         snr_range=(snrs[0], snrs[-1], (snrs[1] - snrs[0]) if len(snrs) > 1 else 0.0), threads=world,
@@ -393,6 +440,13 @@ def build_parser():
     ap.add_argument("--snr-axis", choices=("reference", "esn0", "ebn0"), default=None,
                     help="what the SNR values are: the reference channel has only 'reference'; a channel model "
                          "takes esn0 or ebn0 (default ebn0, with the code's rate and the bits per symbol)")
+    ap.add_argument("--puncture", default=None, metavar="COLS",
+                    help="with --channel awgn / rayleigh: columns not sent and unknown to the receiver, in the "
+                         "frame's order (info 0..k-1, parity k..n-1): comma-separated a, a:b or a:b:step, half-open; "
+                         "a bound is an integer or k / n with +INT / -INT, e.g. k:n:6 or n-48:n")
+    ap.add_argument("--shorten", default=None, metavar="COLS",
+                    help="with --channel awgn / rayleigh: information columns both ends know to be 0, not sent "
+                         "(the same grammar, e.g. 0:24)")
     return ap
 
 
@@ -422,6 +476,8 @@ def parse_args(argv=None):
         ap.error("--max-failed needs --stats-json")
     if a.max_failed < 0:
         ap.error("--max-failed must be >= 0")
+    if (a.puncture is not None or a.shorten is not None) and (a.mode != "physical" or a.channel == "reference"):
+        ap.error("--puncture and --shorten need --mode physical --channel awgn or rayleigh")
     a.llr_scale = 4.0 if a.llr_scale is None else a.llr_scale
     a.alpha = 0.75 if a.alpha is None else a.alpha
     a.beta = 0.5 if a.beta is None else a.beta
@@ -438,6 +494,37 @@ def parse_args(argv=None):
     return a
 
 
+def code_shape(matrix):
+    """(n, k) of what --matrix names, without a device."""
+    if isinstance(matrix, str) and matrix in IRA_CODES:
+        from . import ira
+        m, n = getattr(ira, IRA_CODES[matrix])().shape
+        return n, n - m
+    from .code import EncoderDecoderData, load_committed_code
+    edd = EncoderDecoderData(matrix) if os.path.exists(matrix) else load_committed_code(matrix)
+    return edd._n, edd._k
+
+
+def cli_rate_match(a, shape=None):
+    """The RateMatch of --puncture / --shorten (None without either), validated
+    against the code and the modulation; ValueError otherwise.  shape: the
+    code's (n, k) where the caller has it."""
+    from .ratematch import RateMatch, parse_columns
+    if a.puncture is None and a.shorten is None:
+        return None
+    n, k = shape or code_shape(a.matrix)
+    rm = RateMatch(parse_columns(a.puncture, n, k) if a.puncture is not None else (),
+                   parse_columns(a.shorten, n, k) if a.shorten is not None else ())
+    return rm.validate(n, k, a.channel_spec.bps)
+
+
+def rate_match_header(rm_info, n, k):
+    """The command line's header line of a rate-matched sweep."""
+    return (f"rate matching  E {rm_info['transmitted']} of n {n}  punctured {len(rm_info['punctured'])}  "
+            f"shortened {len(rm_info['shortened'])}  info bits {rm_info['info_bits']} of k {k}  "
+            f"effective rate {rm_info['rate']:.6f}")
+
+
 def main(argv=None):
     a = parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -451,18 +538,24 @@ def main(argv=None):
     snrs = snr_grid(a.initial_snr, a.end_snr, a.step_snr)
     if world > 1 and a.max_failed > 0:
         raise SystemExit("--max-failed needs a single process: failed-frame lists are not gathered across ranks")
+    try:
+        rate_match = cli_rate_match(a)  # the code's n and k without a device
+    except ValueError as e:
+        raise SystemExit(f"--puncture / --shorten: {e}")
     out = simulate(a.matrix, snrs, a.blocks, a.iterations, seed=a.seed, nllr=a.normalized_llr,
                    device=local, rank=rank, world=world, allreduce=allreduce, mode=a.mode, cn_rule=a.cn_rule,
                    schedule=a.schedule, alpha=a.alpha, beta=a.beta, qbits=a.qbits, llr_scale=a.llr_scale,
                    layered_tile=a.layered_tile, quant_tile=a.quant_tile, stats=a.stats_json is not None,
-                   max_failed=a.max_failed, channel=a.channel_spec, snr_axis=a.snr_axis)
+                   max_failed=a.max_failed, channel=a.channel_spec, snr_axis=a.snr_axis, rate_match=rate_match)
     res = out[0]
-    info = channel_info(a.channel_spec, a.snr_axis, snrs, res.config.rate)
+    info = channel_info(a.channel_spec, a.snr_axis, snrs, res.config.rate, rate_match, res.config.n, res.config.k)
     if rank == 0 and a.stats_json is not None:
         stats_to_json(a.stats_json, a.seed, out[2], channel=info)
     if rank == 0:
         print(f"channel {info['model']}  modulation {info['modulation']}  demap {info['demap']}  "
               f"SNR axis {info['snr_axis']}  sigma " + " ".join(f"{x:.6f}" for x in info["sigma"]))
+        if "rate_match" in info:
+            print(rate_match_header(info["rate_match"], res.config.n, res.config.k))
         for sp in res.snr_points:
             print(f"SNR {sp.snr_db:.2f} dB  FER {sp.fer:.6f}  BER {sp.ber:.6e}  "
                   f"ok {sp.successful_blocks}/{sp.total_blocks}  avg conv {sp.avg_convergence_iterations:.3f}")

@@ -24,6 +24,10 @@ package): the ALIST-derived H (utils.py:21-113) as CSR,
 H_std CSR (full for small codes), the column permutation and sha256
 fingerprints of both.
 
+The database's other code shapes (DB_CODES, DB_SETS below): the same record
+per code in db/codes/<name>.npz and one small decode set each in db/<set>.npz
+(`--only db` makes all of them and leaves the five codes above alone).
+
 Usage:  python tests/golden/gen_golden.py [--only NAME ...]
 """
 import argparse
@@ -53,6 +57,40 @@ CODES = {
 FULL_HSTD = {"BCH_7_4_1_strip", "wimax_576_0.5"}
 E_STRIDE = 97
 
+# The database's other shapes (DESIGN.md "Parity decoder on the database's
+# other shapes"): records in db/codes/, one small decode set each in db/.  Kept
+# out of this directory's *.npz and of the package's codes/ on purpose: the
+# parametrized tests over the five codes above glob those.
+DB_OUT = os.path.join(HERE, "db")
+DB_CODES_OUT = os.path.join(DB_OUT, "codes")
+DB_CODES = {
+    "CCSDS_ldpc_n32_k16": "Custom LDPC Codes/CCSDS_ldpc_n32_k16.alist.txt",
+    "Tanner_155_64": "Custom LDPC Codes/Tanner_155_64.alist.txt",
+    "WRAN_N480_K240_R05": "Standardized LDPC Codes/WRAN_N480_K240_P20_R05.txt",
+    "WRAN_N384_K320_R083": "Standardized LDPC Codes/WRAN_N384_K320_P16_R083.txt",
+    "wigig_R05_N672_K336": "Standardized LDPC Codes/wigig_R05_N672_K336.alist.txt",
+    "ieee_802_11ad_n672_r081": "Standardized LDPC Codes/ieee_802_11ad_p42_n672_r081.alist.txt",
+    "wimax_1152_0.83": "Wimax LDPC Codes/wimax_1152_0.83.alist.txt",
+    "wimax_1440_0.5": "Wimax LDPC Codes/wimax_1440_0.5.alist.txt",
+    "wimax_2304_0.66B": "Wimax LDPC Codes/wimax_2304_0.66B.alist.txt",
+    "wimax_2304_0.83": "Wimax LDPC Codes/wimax_2304_0.83.alist.txt",
+}
+# set -> (code, SNRs, normalized-LLR metric, base seed): 4 frames at T = 3 in
+# all, at the SNR(s) where the reference's own 4 frames hold both Result values
+DB_T = 3
+DB_SETS = {
+    "ccsds32_T3": ("CCSDS_ldpc_n32_k16", [-2.0], True, 20000),
+    "tanner155_T3": ("Tanner_155_64", [1.0], True, 21000),
+    "wran480_T3": ("WRAN_N480_K240_R05", [3.5], True, 22000),
+    "wran384_T3": ("WRAN_N384_K320_R083", [1.0], False, 23000),
+    "wigig672_T3": ("wigig_R05_N672_K336", [2.0], True, 24000),
+    "ad672_T3": ("ieee_802_11ad_n672_r081", [1.5], False, 25000),
+    "w1152_83_T3": ("wimax_1152_0.83", [2.0], True, 26000),
+    "w1440_T3": ("wimax_1440_0.5", [2.0], False, 27000),
+    "w2304_66B_T3": ("wimax_2304_0.66B", [2.25], False, 28000),
+    "w2304_83_T3": ("wimax_2304_0.83", [2.5], True, 29000),
+}
+
 _EDD = {}  # name -> EncoderDecoderData (filled in the parent, inherited by fork)
 
 
@@ -70,12 +108,17 @@ def sha16(*arrays):
     return h.hexdigest()
 
 
-def load_code(name):
+def load_code(name, table=None, out_dir=None):
+    """Build the reference's EncoderDecoderData for `name` and write its record.
+    The five package codes carry full H_std by the FULL_HSTD list; a database
+    code (table=DB_CODES) carries it wherever the file stays under MAX_FILE_BYTES."""
+    table = CODES if table is None else table
+    out_dir = CODES_OUT if out_dir is None else out_dir
     _ref_imports()
     from encoder_decoder_data import EncoderDecoderData
     from utils import read_parity_check_matrix
 
-    path = os.path.join(REF_DB, CODES[name])
+    path = os.path.join(REF_DB, table[name])
     t0 = time.time()
     H = read_parity_check_matrix(path).get_sparse_matrix().tocsr()
     edd = EncoderDecoderData(path)
@@ -97,10 +140,15 @@ def load_code(name):
         hstd_sha=np.array(sha16(hs.indptr, hs.indices)),
         perm_sha=np.array(sha16(np.asarray(edd._permutation))),
     )
-    if name in FULL_HSTD:
-        out["hstd_indptr"] = hs.indptr.astype(np.int32)
-        out["hstd_indices"] = hs.indices.astype(np.int32)
-    np.savez_compressed(os.path.join(CODES_OUT, f"{name}.npz"), **out)
+    full = dict(out, hstd_indptr=hs.indptr.astype(np.int32), hstd_indices=hs.indices.astype(np.int32))
+    dst = os.path.join(out_dir, f"{name}.npz")
+    if table is CODES:
+        np.savez_compressed(dst, **(full if name in FULL_HSTD else out))
+        return edd
+    np.savez_compressed(dst, **full)
+    if os.path.getsize(dst) > MAX_FILE_BYTES:
+        np.savez_compressed(dst, **out)
+    assert os.path.getsize(dst) <= MAX_FILE_BYTES, dst
     return edd
 
 
@@ -199,7 +247,7 @@ def run_frame(job):
     )
 
 
-def run_set(pool, set_name, code, T, snrs, frames, nllr, base_seed, overrides=None):
+def run_set(pool, set_name, code, T, snrs, frames, nllr, base_seed, overrides=None, out_dir=HERE):
     jobs = []
     meta_snr = []
     for si, snr in enumerate(snrs):
@@ -230,7 +278,7 @@ def run_set(pool, set_name, code, T, snrs, frames, nllr, base_seed, overrides=No
     )
     rec["E"] = E_all if code == "BCH_7_4_1_strip" else E_all[:, ::E_STRIDE].copy()
     del full_e
-    save_set(set_name, rec)
+    save_set(set_name, rec, out_dir)
     print(f"[{set_name}] {len(jobs)} frames in {time.time()-t0:.1f}s; "
           f"ok={rec['ok'].mean():.3f} conv>=0:{(rec['conv']>=0).sum()}", flush=True)
 
@@ -278,6 +326,10 @@ def main():
     for name in CODES:
         if name in need:
             load_code(name)
+    os.makedirs(DB_CODES_OUT, exist_ok=True)
+    for name in DB_CODES:  # --only db: all ten records and sets; or name single sets
+        if want("db") or any(want(s) for s, v in DB_SETS.items() if v[0] == name):
+            load_code(name, DB_CODES, DB_CODES_OUT)
 
     ctx = mp.get_context("fork")
     rng = np.random.default_rng(20260213)
@@ -309,6 +361,9 @@ def main():
             run_set(pool, "w2304A_T3_4dB", "wimax_2304_0.75A", 3, [4.0], 4, False, 10000)
         if want("w2304B_T2"):
             run_set(pool, "w2304B_T2", "wimax_2304_0.75B", 2, [2.0], 2, False, 11000)
+        for set_name, (code, snrs, nllr, base_seed) in DB_SETS.items():
+            if code in _EDD:
+                run_set(pool, set_name, code, DB_T, snrs, 4 // len(snrs), nllr, base_seed, out_dir=DB_OUT)
 
 
 if __name__ == "__main__":

@@ -70,6 +70,16 @@ def _tile_name(code, layout):
 _GRAPHS = {}
 
 
+def _hstd(code):
+    """H_std of a shipped code, of one of the database's other shapes
+    (tests/db_codes.py) or a synthetic limit graph (tests/parity_graphs.py)."""
+    import db_codes
+    import parity_graphs
+    if code in db_codes.CODES:
+        return db_codes.db_hstd(code)
+    return parity_graphs.graph(code) if code in parity_graphs.NAMES else hstd_for(code)
+
+
 def _graph(code, layout, monkeypatch):
     from ldpc_amd.device import Graph
     key = (code, layout)
@@ -79,7 +89,7 @@ def _graph(code, layout, monkeypatch):
         if layout == "8p":  # tile8's pair form (two rows per wavefront)
             monkeypatch.setenv("LDPC_T8_PAIR", "1")
         try:
-            _GRAPHS[key] = Graph(hstd_for(code))
+            _GRAPHS[key] = Graph(_hstd(code))
         finally:
             if layout is not None:
                 monkeypatch.delenv("LDPC_TILE8")
@@ -88,12 +98,17 @@ def _graph(code, layout, monkeypatch):
     return _GRAPHS[key]
 
 
-def _run_route(code, layout, route, llr, T, monkeypatch, **kw):
+def _run_route(code, layout, route, llr, T, monkeypatch, tile_name=None, instead=None, **kw):
     """Decode through one route; assert from the profile that it ran and
-    nothing else did.  -> DecodeResult."""
+    nothing else did.  -> DecodeResult.  tile_name: the tile-resident kernel
+    the graph must report (default: _tile_name's table of the shipped codes);
+    instead: the kinds that must run where the forced route cannot serve the
+    graph and the call has to take another one."""
     from ldpc_amd import _lib
     from ldpc_amd.device import Decoder
     env, split, must = ROUTES[route]
+    if instead is not None:
+        must = instead
     g = _graph(code, layout, monkeypatch)
     dec = Decoder(g, len(llr))
     for k, v in env.items():
@@ -109,9 +124,9 @@ def _run_route(code, layout, route, llr, T, monkeypatch, **kw):
     for kind in _ALL:
         ran = p[kind][1] > 0
         assert ran == (kind in must), (route, layout, kind, p)
-    if route == "tile":
+    if route == "tile" and instead is None:
         assert p["tile"][1] == 1, p  # one launch: the whole batch, every iteration
-        assert _lib.lib().ldpc_tile_kernel_name(g.handle).decode() == _tile_name(code, layout)
+        assert _lib.lib().ldpc_tile_kernel_name(g.handle).decode() == (tile_name or _tile_name(code, layout))
     dec.close()
     return r
 

@@ -358,6 +358,76 @@ const char *ldpc_phys_kernel_name_q(const ldpc_graph *g, uint32_t flags, int32_t
 /* LDS bytes of a frame's quantized state under a schedule (-1: bad arguments). */
 int64_t ldpc_phys_q_lds_bytes(const ldpc_graph *g, int32_t schedule);
 
+/* ------------------------------------ physical mode, bit-flipping decoders
+ * The hard-decision baseline (csrc/phys_bitflip.hip): parallel gradient-descent
+ * bit flipping (Wadayama et al.), one family with two parameters, weight w >= 0
+ * and theta.  w = 0 is plain hard-decision bit flipping; with theta = 0 that is
+ * the majority rule (flip a bit when more than half of its checks fail).  The
+ * reference advertises such a decoder (LDPCDecoderType.BIT_FLIPPING,
+ * --decoder bitflipping) and never dispatches one.
+ * All arithmetic is fp32 and every operation rounds once.  Any graph
+ * ldpc_graph_create accepts: empty rows, empty columns and degree-1 rows are
+ * fine.  d_j is the degree of column j.
+ *   init:  Lam_j = -(float)llr_j (lam_j for on-device frames), b_j = (Lam_j < 0);
+ *          -0.0 gives 0, so a punctured column (llr = +0.0) starts as bit 0;
+ *   iteration it = 0 .. max_iter - 1:
+ *     1. s_r = XOR of b over row r's columns;
+ *     2. if any s_r is 1:  u_j = sum of s_r over column j's rows,
+ *          c_j = b_j ? -Lam_j : Lam_j,
+ *          Delta_j = fl(fl(w * c_j) + (float)(d_j - 2 u_j));
+ *          when w == 0 the product term is ABSENT, Delta_j = (float)(d_j - 2 u_j):
+ *          Lam is then used for nothing but the initial b, so a non-finite
+ *          LLR cannot make the two kernels differ;
+ *          every j with Delta_j < theta flips, all from the same s; s is recomputed;
+ *     3. if no s_r is 1: conv = it, stop.
+ *   So a frame whose channel hard decisions already form a codeword has conv 0
+ *   and no flips.
+ *   outputs:  z = b ^ 1; status = 0 if converged, else 1; conv = -1 if not
+ *          converged; iters = conv + 1, or max_iter if not converged; synw = sum of
+ *          s_r at exit (0 when converged).
+ * Two kernels, identical outputs and counters.  "bitflip_kernel": one frame per
+ * workgroup, Lam[n] fp32 and b[n], s[m] as bytes in LDS, any w.
+ * "bitflip_sliced_kernel": w == 0 only; 64 frames per workgroup, one 64-bit
+ * word per column and per row in LDS (bit f = frame f of the tile); the flip
+ * rule becomes u_j >= t(d_j) with t(d) the smallest u in 0..d with
+ * (float)(d - 2u) < theta by that same fp32 comparison (d + 1, "never", if there
+ * is none), u_j of 64 frames counted in bit planes.  It runs when w == 0, every
+ * column degree is <= 63, its 8 (n + m) bytes (plus scratch) fit LDS, the run
+ * collects no Monte-Carlo statistics and LDPC_F_BF_GENERIC is not set; else the
+ * per-frame kernel does.  Neither has an HBM path: a graph whose state does
+ * not fit LDS (4n + n + m bytes for the per-frame kernel; the DVB-S2 profile,
+ * n = 64800) is LDPC_ERANGE.
+ * LDPC_EINVAL, before any device work: NULL graph, decoder or counters;
+ * batch < 1; NULL llr; max_iter < 1; weight not finite or < 0; theta not
+ * finite; any flag other than LDPC_F_DEVICE_PTRS and LDPC_F_BF_GENERIC
+ * (ldpc_bf_mc_run takes no LDPC_F_DEVICE_PTRS).
+ * The results equal a numpy fp32 restatement of these rules (tests/bitflip_ref.py). */
+#define LDPC_F_BF_GENERIC 0x100u /* the per-frame kernel even where the sliced one applies (tests, A/B) */
+/* llr [batch][n] fp64.  z_out [batch][n]; conv_out, status_out, iters_out,
+ * synw_out [batch]; every output pointer may be NULL.  Host pointers are staged,
+ * copied and synchronised; LDPC_F_DEVICE_PTRS: device pointers, launched
+ * asynchronously on `stream`. */
+int ldpc_bf_decode(const ldpc_graph *g, int32_t batch, const double *llr, int32_t max_iter, uint32_t flags,
+                   float weight, float theta, uint8_t *z_out, int32_t *conv_out, int32_t *status_out,
+                   int32_t *iters_out, int32_t *synw_out, void *stream);
+/* ldpc_phys_mc_run with a bit-flipping decoder: exactly its frame source
+ * (d_std on H_std or on the IRA graph itself, the same shape checks, the
+ * decoder's channel and rate-matching pattern; frames as fp32 Lambda rows).
+ * The seven counters keep their meaning; slot [5] is 0.  While
+ * ldpc_mc_stats_enable is on, the run fills the statistics as the other
+ * physical runs do (ldpc_mc_stats_read unchanged) and uses the per-frame
+ * kernel for it, also where the sliced one would apply.  The decode launches
+ * are timed under LDPC_K_PHYS. */
+int ldpc_bf_mc_run(ldpc_decoder *d_std, const ldpc_graph *g_phys, uint64_t seed, int32_t n_points,
+                   const double *sigmas, int64_t frames_per_point, int64_t frame0, int32_t max_iter,
+                   uint32_t flags, float weight, float theta, int64_t *counters_out, void *stream);
+/* The kernel ldpc_bf_decode runs: "bitflip_sliced_kernel", "bitflip_kernel", or
+ * "" when the state does not fit LDS or an argument is invalid (the launch's
+ * own decision; a Monte-Carlo run with statistics on runs "bitflip_kernel"). */
+const char *ldpc_bf_kernel_name(const ldpc_graph *g, uint32_t flags, float weight);
+/* Dynamic LDS bytes of that kernel's workgroup (-1: bad arguments). */
+int64_t ldpc_bf_lds_bytes(const ldpc_graph *g, uint32_t flags, float weight);
+
 /* ------------------------------------------------------------ profiling
  * HIP-event timing of the decoder's own launches, on the stream they are
  * launched on (used by bench.py for the live roofline).  While enabled, every

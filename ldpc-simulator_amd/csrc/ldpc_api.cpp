@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cfloat>
 #include <climits>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -2266,6 +2267,194 @@ int ldpc_phys_mc_run_q(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int
             HIP_TRY(timed(d, LDPC_K_PHYS, s, [&] {
                 return ldpc::launch_phys_quant(P, nullptr, rows, cnt, max_iter, nullptr, nullptr, nullptr, nullptr,
                                                nullptr, st.ubits, ctr, phys_quant_max_grid(), s, rule, ms);
+            }));
+        }
+    }
+    std::vector<unsigned long long> h(need);
+    HIP_TRY(hipMemcpyAsync(h.data(), d->counters, sizeof(unsigned long long) * need, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int i = 0; i < need; ++i) counters_out[i] = (int64_t)h[i];
+    if (d->ms_on) d->ms_state = 1;
+    return LDPC_OK;
+}
+
+// ------------------------------------------- physical mode, bit flipping
+namespace {
+
+enum BfKernel { kBfNone = 0, kBfSliced, kBfGeneric };
+
+// The kernel a bit-flipping launch on graph P runs (stats: the run collects
+// Monte-Carlo statistics, which only the per-frame kernel does).
+BfKernel bf_kernel(const DevGraph &P, uint32_t flags, float weight, bool stats) {
+    if (weight == 0.0f && !(flags & LDPC_F_BF_GENERIC) && !stats && ldpc::bitflip_sliced_applies(P) &&
+        ldpc::bitflip_sliced_lds_bytes(P) + 1024 <= kLdsLimit)
+        return kBfSliced;
+    return ldpc::bitflip_lds_bytes(P) + 64 <= kLdsLimit ? kBfGeneric : kBfNone;
+}
+
+size_t bf_lds(const DevGraph &P, BfKernel k) {
+    return k == kBfSliced ? ldpc::bitflip_sliced_lds_bytes(P) + 1024 : ldpc::bitflip_lds_bytes(P) + 64;
+}
+
+// workgroups the device holds at once (as phys_grid), at most `work` (frames, or 64-frame tiles)
+int bf_grid(const DevGraph &P, BfKernel k, int work) {
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) {
+        hipDeviceProp_t p;
+        if (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) cus = p.multiProcessorCount;
+    }
+    const int waves = ldpc::bitflip_threads() / 64;
+    int per_cu = (int)std::min<size_t>(32 / waves, kLdsLimit / bf_lds(P, k));
+    if (per_cu < 1) per_cu = 1;
+    return (int)std::min<int64_t>((int64_t)cus * per_cu, work);
+}
+
+int bf_check(const char *fn, uint32_t flags, uint32_t allowed, float weight, float theta) {
+    if (flags & ~allowed) return ldpc_fail(LDPC_EINVAL, "%s: unsupported flags 0x%x", fn, flags & ~allowed);
+    if (!std::isfinite(weight) || weight < 0.0f)
+        return ldpc_fail(LDPC_EINVAL, "%s: weight must be finite and >= 0, got %g", fn, (double)weight);
+    if (!std::isfinite(theta)) return ldpc_fail(LDPC_EINVAL, "%s: theta must be finite, got %g", fn, (double)theta);
+    return LDPC_OK;
+}
+
+int bf_no_fit(const char *fn, const DevGraph &P) {
+    return ldpc_fail(LDPC_ERANGE, "%s: a frame's bit-flipping state (%zu bytes for n = %d, m = %d) does not fit LDS; "
+                                  "an HBM path for bit flipping is not implemented", fn, ldpc::bitflip_lds_bytes(P),
+                     P.n, P.m);
+}
+
+hipError_t bf_launch(const DevGraph &P, BfKernel k, const double *llr, const float *lam, int layout, int count,
+                     int max_iter, uint8_t *z, int *conv, int *status, int *iters, int *synw, const uint32_t *ubits,
+                     unsigned long long *ctr, hipStream_t s, float weight, float theta,
+                     const ldpc::McStats &ms = ldpc::McStats{}) {
+    ldpc::BitflipRule rule;
+    rule.weight = weight;
+    rule.theta = theta;
+    rule.sliced = k == kBfSliced;
+    const int work = rule.sliced ? (count + kTile - 1) / kTile : count;
+    return ldpc::launch_bitflip(P, llr, lam, layout, count, max_iter, z, conv, status, iters, synw, ubits, ctr,
+                                bf_grid(P, k, work), s, rule, ms);
+}
+
+}  // namespace
+
+const char *ldpc_bf_kernel_name(const ldpc_graph *g, uint32_t flags, float weight) {
+    if (!g || (flags & ~(uint32_t)(LDPC_F_DEVICE_PTRS | LDPC_F_BF_GENERIC)) || !std::isfinite(weight) || weight < 0.0f)
+        return "";
+    switch (bf_kernel(g->dg, flags, weight, false)) {
+    case kBfSliced: return "bitflip_sliced_kernel";
+    case kBfGeneric: return "bitflip_kernel";
+    default: return "";
+    }
+}
+
+int64_t ldpc_bf_lds_bytes(const ldpc_graph *g, uint32_t flags, float weight) {
+    if (!g || (flags & ~(uint32_t)(LDPC_F_DEVICE_PTRS | LDPC_F_BF_GENERIC)) || !std::isfinite(weight) || weight < 0.0f)
+        return -1;
+    const BfKernel k = bf_kernel(g->dg, flags, weight, false);
+    return (int64_t)(k == kBfSliced ? ldpc::bitflip_sliced_lds_bytes(g->dg) : ldpc::bitflip_lds_bytes(g->dg));
+}
+
+int ldpc_bf_decode(const ldpc_graph *g, int32_t batch, const double *llr, int32_t max_iter, uint32_t flags,
+                   float weight, float theta, uint8_t *z_out, int32_t *conv_out, int32_t *status_out,
+                   int32_t *iters_out, int32_t *synw_out, void *stream) {
+    const char *fn = "ldpc_bf_decode";
+    if (!g) return ldpc_fail(LDPC_EINVAL, "%s: NULL graph", fn);
+    if (batch < 1 || max_iter < 1 || !llr)
+        return ldpc_fail(LDPC_EINVAL, "%s: bad arguments (batch=%d max_iter=%d)", fn, batch, max_iter);
+    if (int rc = bf_check(fn, flags, LDPC_F_DEVICE_PTRS | LDPC_F_BF_GENERIC, weight, theta)) return rc;
+    const DevGraph &G = g->dg;
+    const BfKernel k = bf_kernel(G, flags, weight, false);
+    if (k == kBfNone) return bf_no_fit(fn, G);
+    DeviceGuard dg(g->device);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = (size_t)G.n, B = (size_t)batch;
+    auto launch = [&](const double *in, uint8_t *z, int *conv, int *status, int *iters, int *synw) {
+        return bf_launch(G, k, in, nullptr, 0, batch, max_iter, z, conv, status, iters, synw, nullptr, nullptr, s,
+                         weight, theta);
+    };
+    if (flags & LDPC_F_DEVICE_PTRS) {
+        HIP_TRY(launch(llr, z_out, conv_out, status_out, iters_out, synw_out));
+        return LDPC_OK;
+    }
+    double *d_llr = nullptr;
+    uint8_t *d_z = nullptr;
+    int *d_i = nullptr;
+    int rc = dev_alloc(&d_llr, B * n);
+    if (!rc) rc = dev_alloc(&d_z, B * n);
+    if (!rc) rc = dev_alloc(&d_i, 4 * B);
+    hipError_t e = hipSuccess;
+    if (!rc) {
+        e = hipMemcpyAsync(d_llr, llr, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
+        if (!e) e = launch(d_llr, d_z, d_i, d_i + B, d_i + 2 * B, d_i + 3 * B);
+        if (!e && z_out) e = hipMemcpyAsync(z_out, d_z, B * n, hipMemcpyDeviceToHost, s);
+        if (!e && conv_out) e = hipMemcpyAsync(conv_out, d_i, sizeof(int) * B, hipMemcpyDeviceToHost, s);
+        if (!e && status_out) e = hipMemcpyAsync(status_out, d_i + B, sizeof(int) * B, hipMemcpyDeviceToHost, s);
+        if (!e && iters_out) e = hipMemcpyAsync(iters_out, d_i + 2 * B, sizeof(int) * B, hipMemcpyDeviceToHost, s);
+        if (!e && synw_out) e = hipMemcpyAsync(synw_out, d_i + 3 * B, sizeof(int) * B, hipMemcpyDeviceToHost, s);
+        if (!e) e = hipStreamSynchronize(s);
+        if (e) rc = ldpc_fail(LDPC_EDEVICE, "%s: %s", fn, hipGetErrorString(e));
+    }
+    (void)hipFree(d_llr);
+    (void)hipFree(d_z);
+    (void)hipFree(d_i);
+    return rc;
+}
+
+int ldpc_bf_mc_run(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int32_t n_points, const double *sigmas,
+                   int64_t frames_per_point, int64_t frame0, int32_t max_iter, uint32_t flags, float weight,
+                   float theta, int64_t *counters_out, void *stream) {
+    const char *fn = "ldpc_bf_mc_run";
+    if (!gp) return ldpc_fail(LDPC_EINVAL, "%s: NULL graph", fn);
+    if (!d || n_points <= 0 || !sigmas || frames_per_point < 0 || frame0 < 0 || max_iter < 1 || !counters_out)
+        return ldpc_fail(LDPC_EINVAL, "%s: bad arguments", fn);
+    if (int rc = bf_check(fn, flags, LDPC_F_BF_GENERIC, weight, theta)) return rc;
+    const DevGraph &G = d->g->dg;
+    const DevGraph &P = gp->dg;
+    if (!G.std_form && !(G.ira && d->g == gp))
+        return ldpc_fail(LDPC_EINVAL,
+                         "%s: the decoder's graph must be the code's H_std = [A | I_m], or the "
+                         "IRA graph itself", fn);
+    if (P.n != G.n || P.k != G.k)
+        return ldpc_fail(LDPC_EINVAL, "%s: physical graph shape %dx%d != %dx%d", fn, P.m, P.n, G.m, G.n);
+    for (int p = 0; p < n_points; ++p)
+        if (!(sigmas[p] > 0.0)) return ldpc_fail(LDPC_EINVAL, "%s: sigma[%d] <= 0", fn, p);
+    if (int rc = channel_frames_check(fn, d, 0)) return rc;
+    // the statistics are the per-frame kernel's
+    const BfKernel k = bf_kernel(P, flags, weight, d->ms_on);
+    if (k == kBfNone) return bf_no_fit(fn, P);
+    DeviceGuard dg(d->g->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = ensure_pbits(d, G)) return rc;
+    ldpc::RateMatchDev rm;
+    if (int rc = rate_match_dev(d, s, &rm)) return rc;
+    const int need = n_points * LDPC_MC_NCOUNT;
+    if (d->counters_cap < need) {
+        (void)hipFree(d->counters);
+        d->counters = nullptr;
+        d->counters_cap = 0;
+        if (int rc = dev_alloc(&d->counters, (size_t)need + 1)) return rc;
+        d->counters_cap = need;
+    }
+    HIP_TRY(hipMemsetAsync(d->counters, 0, sizeof(unsigned long long) * need, s));
+    if (int rc = mc_stats_begin(d, n_points, max_iter, false, s)) return rc;
+    const int64_t cap = (int64_t)d->cap_tiles * kTile;
+    for (int p = 0; p < n_points; ++p) {
+        unsigned long long *ctr = d->counters + (size_t)p * LDPC_MC_NCOUNT;
+        for (int64_t start = 0; start < frames_per_point; start += cap) {
+            const int cnt = (int)std::min<int64_t>(cap, frames_per_point - start);
+            state_bind(d, (cnt + kTile - 1) / kTile, cnt);
+            const DevState st = d->st;
+            ldpc::McStats ms;
+            mc_stats_point(d, p, frame0 + start, &ms);
+            float *rows = (float *)d->llr_stage;  // the frames as fp32 Lambda rows, as ldpc_phys_mc_run's LDS path
+            HIP_TRY(timed(d, LDPC_K_GEN, s, [&] {
+                return ldpc::launch_frames(G, st, phys_tile(d), seed, p, sigmas[p], frame0 + start,
+                                           ldpc::kFramesRowLambda, rows, d->chan, s, rm);
+            }));
+            HIP_TRY(timed(d, LDPC_K_PHYS, s, [&] {
+                return bf_launch(P, k, nullptr, rows, 2, cnt, max_iter, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                 st.ubits, ctr, s, weight, theta, ms);
             }));
         }
     }

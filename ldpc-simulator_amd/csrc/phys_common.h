@@ -1,5 +1,6 @@
 // phys_common.h -- what the LDS-resident physical-mode kernels share
-// (phys_kernels.hip: flooding; phys_layered.hip: layered min-sum): the kernel
+// (phys_kernels.hip: flooding; phys_layered.hip: layered min-sum;
+// phys_bitflip.hip: bit flipping): the kernel
 // arguments, a frame's load into LDS, its outputs and Monte-Carlo counters, and
 // the min-sum check rule (also used by phys_tile.hip).
 #pragma once
@@ -140,6 +141,54 @@ __device__ __forceinline__ void frame_finish(const PhysArgs &a, const McStats &m
             for (int j = tid; j < g.k; j += nt) {
                 const uint32_t w = a.ubits[((size_t)(f >> 6) * kw + (j >> 5)) * kTile + (f & 63)];
                 my += (((w >> (j & 31)) & 1u) != (L[j] < 0.0f ? 1u : 0u)) ? 1 : 0;
+            }
+            atomicAdd(s_err, my);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            fc.v[0] += 1ull;
+            if (conv < 0) {
+                fc.v[1] += 1ull;
+                fc.v[2] += (unsigned long long)*s_err;
+            } else {
+                fc.v[3] += (unsigned long long)conv;
+                fc.v[4] += 1ull;
+            }
+            fc.v[6] += (unsigned long long)iters;
+            if constexpr (stats) mc_stats_frame(ms, ms.frame_base + f, conv, *s_err, s_bins);
+        }
+    }
+    __syncthreads();  // LDS reused by the next frame
+}
+
+// frame_finish for a decoder whose state is the hard decisions themselves
+// (phys_bitflip.hip): bits[j] = frame f's bit estimate b_j (0 / 1), no posterior.
+// Same outputs, counters and statistics; synw_out[f] (or null) = synw, the
+// syndrome weight the caller counted at exit.
+template <bool STATS>
+__device__ __forceinline__ void frame_finish_bits(const PhysArgs &a, const McStats &ms, int f, int conv,
+                                                  const uint8_t *bits, int synw, int *synw_out, int *s_err,
+                                                  unsigned *s_bins, int tid, int nt, FrameCounts &fc) {
+    const DevGraph &g = a.g;
+    const int iters = conv >= 0 ? conv + 1 : a.max_iter;
+    if (a.z_out)
+        for (int j = tid; j < g.n; j += nt) a.z_out[(size_t)f * g.n + j] = bits[j] ^ 1;
+    if (tid == 0) {
+        if (a.conv_out) a.conv_out[f] = conv;
+        if (a.status_out) a.status_out[f] = conv >= 0 ? 0 : 1;
+        if (a.iters_out) a.iters_out[f] = iters;
+        if (synw_out) synw_out[f] = synw;
+        *s_err = 0;
+    }
+    if (a.ctr) {
+        __syncthreads();
+        constexpr bool stats = STATS;
+        if (conv < 0 || stats) {  // as frame_finish: failed frames, and every frame for the statistics
+            const int kw = (g.k + 31) >> 5;
+            int my = 0;
+            for (int j = tid; j < g.k; j += nt) {
+                const uint32_t w = a.ubits[((size_t)(f >> 6) * kw + (j >> 5)) * kTile + (f & 63)];
+                my += (((w >> (j & 31)) & 1u) != (uint32_t)bits[j]) ? 1 : 0;
             }
             atomicAdd(s_err, my);
         }

@@ -278,6 +278,25 @@ hipError_t launch_phys_quant(const DevGraph &g, const double *llr, const float *
                              unsigned long long *ctr, int max_grid, hipStream_t s, const QuantRule &rule,
                              const McStats &ms = McStats{});
 
+// bit-flipping decoders (phys_bitflip.hip): Delta_j = w c_j + (d_j - 2 u_j), flip where Delta_j < theta.
+// sliced: bitflip_sliced_kernel, 64 frames per workgroup as one 64-bit word per
+// column (w == 0, bitflip_sliced_applies, no statistics); else bitflip_kernel,
+// one frame per workgroup.  Both keep a frame's / a tile's whole state in LDS.
+struct BitflipRule {
+    float weight = 0.0f;
+    float theta = 0.0f;
+    bool sliced = false;
+};
+size_t bitflip_lds_bytes(const DevGraph &g);         // bitflip_kernel: Lam[n] fp32, b[n] and s[m] bytes
+size_t bitflip_sliced_lds_bytes(const DevGraph &g);  // bitflip_sliced_kernel: 8 (n + m)
+bool bitflip_sliced_applies(const DevGraph &g);      // every column degree <= 63
+int bitflip_threads();                               // threads per workgroup of both kernels
+// input layouts as launch_phys; synw [count] or null: the syndrome weight at exit
+hipError_t launch_bitflip(const DevGraph &g, const double *llr, const float *lam, int layout, int count, int max_iter,
+                          uint8_t *z, int *conv, int *status, int *iters, int *synw, const uint32_t *ubits,
+                          unsigned long long *ctr, int grid, hipStream_t s, const BitflipRule &rule,
+                          const McStats &ms = McStats{});
+
 // physical mode, HBM-resident tiles + IRA frame source (phys_tile.hip)
 // on-device frames of a chunk (frame_kernels.hip): info bits -> st.ubits,
 // parities via pt.pbits/pt.wpar (H_std [A|I] or IRA graph), channel LLRs as

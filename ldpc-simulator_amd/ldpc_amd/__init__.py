@@ -20,7 +20,7 @@ def __getattr__(name):  # lazy: the decoder classes touch the GPU only when used
     if name == "SPA_Decoder":
         from .spa_decoder import SPA_Decoder
         return SPA_Decoder
-    if name in ("Graph", "Decoder"):
+    if name in ("Graph", "Decoder", "bitflip_decode"):
         from . import device
         return getattr(device, name)
     raise AttributeError(name)

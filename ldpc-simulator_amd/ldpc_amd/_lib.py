@@ -30,6 +30,7 @@ LDPC_F_SPLIT = 0x10
 LDPC_F_TEST_ZERO = 0x20  # test only: frame-source erasures (include/ldpc_hip.h)
 LDPC_F_LAYERED_TILE = 0x40  # layered schedule on the HBM tile kernels even if the state fits LDS
 LDPC_F_QUANT_TILE = 0x80  # fixed-point decoder on the HBM tile kernels even if the state fits LDS
+LDPC_F_BF_GENERIC = 0x100  # bit flipping: the per-frame kernel even where the sliced one applies
 LDPC_MC_NCOUNT = 7
 LDPC_EINVAL = -22  # include/ldpc_hip.h error codes used on the Python side
 LDPC_ERANGE = -34
@@ -51,6 +52,7 @@ EXPORTED = (
     "ldpc_phys_lds_bytes", "ldpc_phys_decode", "ldpc_phys_mc_run",
     "ldpc_phys_decode_ex", "ldpc_phys_mc_run_ex", "ldpc_phys_kernel_name_ex", "ldpc_layers_build",
     "ldpc_phys_decode_q", "ldpc_phys_mc_run_q", "ldpc_phys_kernel_name_q", "ldpc_phys_q_lds_bytes",
+    "ldpc_bf_decode", "ldpc_bf_mc_run", "ldpc_bf_kernel_name", "ldpc_bf_lds_bytes",
     "ldpc_comm_unique_id", "ldpc_comm_init", "ldpc_comm_allreduce", "ldpc_comm_barrier", "ldpc_comm_destroy",
     "ldpc_device_synchronize",
 )
@@ -123,6 +125,12 @@ def _declare(lib):
                                               c_i32, c_i32, c_i32, c_flt, c_i32, P(c_i64), c_vp]),
         "ldpc_phys_kernel_name_q": (ctypes.c_char_p, [c_vp, c_u32, c_i32, c_i32, c_i32]),
         "ldpc_phys_q_lds_bytes": (c_i64, [c_vp, c_i32]),
+        "ldpc_bf_decode": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32, c_u32, c_flt, c_flt, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                          c_vp]),
+        "ldpc_bf_mc_run": (ctypes.c_int, [c_vp, c_vp, c_u64, c_i32, P(c_dbl), c_i64, c_i64, c_i32, c_u32, c_flt, c_flt,
+                                          P(c_i64), c_vp]),
+        "ldpc_bf_kernel_name": (ctypes.c_char_p, [c_vp, c_u32, c_flt]),
+        "ldpc_bf_lds_bytes": (c_i64, [c_vp, c_u32, c_flt]),
         "ldpc_layers_build": (ctypes.c_int, [c_i32, c_i32, P(c_i32), P(c_i32), P(c_i32), P(c_i32)]),
         "ldpc_profile_read": (ctypes.c_int, [c_vp, P(c_dbl), P(c_i64)]),
         "ldpc_rare_rows_read": (ctypes.c_int, [c_vp, P(c_i64)]),

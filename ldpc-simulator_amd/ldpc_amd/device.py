@@ -18,8 +18,8 @@ import numpy as np
 from scipy import sparse
 
 from . import _lib
-from ._lib import (LDPC_EINVAL, LDPC_ERANGE, LDPC_F_DEVICE_PTRS, LDPC_F_LAYERED_TILE, LDPC_F_NLLR, LDPC_F_PHYS_HBM,
-                   LDPC_F_QUANT_TILE, LDPC_F_SPLIT, LDPC_F_STATIC, LDPC_MC_NCOUNT, LdpcError, as_i32, check)
+from ._lib import (LDPC_EINVAL, LDPC_ERANGE, LDPC_F_BF_GENERIC, LDPC_F_DEVICE_PTRS, LDPC_F_LAYERED_TILE, LDPC_F_NLLR,
+                   LDPC_F_PHYS_HBM, LDPC_F_QUANT_TILE, LDPC_F_SPLIT, LDPC_F_STATIC, LDPC_MC_NCOUNT, LdpcError, as_i32, check)
 
 
 def _csr_arrays(H):
@@ -235,6 +235,53 @@ class DecodeResult(dict):
     __getattr__ = dict.__getitem__
 
 
+def bitflip_args(weight=0.0, theta=0.0):
+    """(weight, theta) of the bit-flipping entries (ldpc_bf_decode) as floats:
+    weight finite and >= 0, theta finite, both also as the fp32 values the
+    decoder computes with.  Raises ValueError otherwise -- before any device
+    call."""
+    try:
+        weight, theta = float(weight), float(theta)
+    except (TypeError, ValueError):
+        raise ValueError(f"weight and theta must be numbers, got {weight!r}, {theta!r}")
+    with np.errstate(over="ignore"):
+        w32, t32 = np.float32(weight), np.float32(theta)
+    if not (np.isfinite(weight) and np.isfinite(w32) and weight >= 0.0):
+        raise ValueError(f"weight must be finite and >= 0 (in fp32), got {weight}")
+    if not (np.isfinite(theta) and np.isfinite(t32)):
+        raise ValueError(f"theta must be finite (in fp32), got {theta}")
+    return weight, theta
+
+
+def bitflip_kernel_name(graph, weight=0.0, generic=False):
+    """Measurement label: the kernel bitflip_decode runs for these options
+    ("bitflip_sliced_kernel", "bitflip_kernel", or "" when the state does not
+    fit LDS)."""
+    weight, _ = bitflip_args(weight)
+    return _lib.gpu().ldpc_bf_kernel_name(graph.handle, LDPC_F_BF_GENERIC if generic else 0, weight).decode()
+
+
+def bitflip_decode(graph, llr, max_iter, weight=0.0, theta=0.0, generic=False):
+    """Bit-flipping decode of [B, n] LLRs on a sparse graph (H[:, perm]):
+    parallel gradient-descent bit flipping with Delta_j = weight * c_j +
+    (d_j - 2 u_j), flip where Delta_j < theta (include/ldpc_hip.h
+    "bit-flipping decoders"); weight = 0 is plain hard-decision flipping, with
+    theta = 0 the majority rule.  generic=True runs the per-frame kernel even
+    where the bit-sliced one applies.  Returns DecodeResult(z, conv, status,
+    iters, synw); synw is the syndrome weight at exit."""
+    weight, theta = bitflip_args(weight, theta)
+    llr = np.ascontiguousarray(np.atleast_2d(np.asarray(llr, dtype=np.float64)))
+    B, n = llr.shape
+    if n != graph.n:
+        raise ValueError(f"llr must be [batch, {graph.n}]")
+    z = np.empty((B, n), np.uint8)
+    conv, status, iters, synw = (np.empty(B, np.int32) for _ in range(4))
+    check("ldpc_bf_decode", _lib.gpu().ldpc_bf_decode(
+        graph.handle, B, _lib.ptr(llr), int(max_iter), LDPC_F_BF_GENERIC if generic else 0, weight, theta,
+        _lib.ptr(z), _lib.ptr(conv), _lib.ptr(status), _lib.ptr(iters), _lib.ptr(synw), None))
+    return DecodeResult(z=z, conv=conv, status=status, iters=iters, synw=synw)
+
+
 class Decoder:
     """Device workspace for chunks of up to `max_frames` frames."""
 
@@ -431,6 +478,21 @@ class Decoder:
             check("ldpc_phys_mc_run", _lib.gpu().ldpc_phys_mc_run(*head, *tail))
         else:
             check("ldpc_phys_mc_run_ex", _lib.gpu().ldpc_phys_mc_run_ex(*head, rule, sched, param, *tail))
+        return out
+
+    def bitflip_mc_run(self, phys_graph, seed, sigmas, frames_per_point, frame0, max_iter, weight=0.0, theta=0.0,
+                       generic=False):
+        """phys_mc_run with a bit-flipping decoder (ldpc_bf_mc_run): the same
+        on-device frames, channel and rate-matching pattern, the same seven
+        counters.  weight / theta / generic as bitflip_decode; with mc_stats on
+        the run uses the per-frame kernel."""
+        weight, theta = bitflip_args(weight, theta)
+        sig = np.ascontiguousarray(np.asarray(sigmas, dtype=np.float64))
+        out = np.zeros((len(sig), LDPC_MC_NCOUNT), np.int64)
+        check("ldpc_bf_mc_run", _lib.gpu().ldpc_bf_mc_run(
+            self._h, phys_graph.handle, int(seed), len(sig), sig.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+            int(frames_per_point), int(frame0), int(max_iter), LDPC_F_BF_GENERIC if generic else 0, weight, theta,
+            out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), None))
         return out
 
     KINDS = ("cn", "vn", "generate", "count", "phys", "phys_cn", "phys_vn", "tile", "cn_edge", "vn_edge",

@@ -187,10 +187,42 @@ def decoder_type(cn_rule="spa", schedule="flooding", qbits=None):
             + (f"-q{int(qbits)}" if qbits is not None else ""))
 
 
+DECODERS = ("sumproduct", "bitflipping")  # the reference's --decoder values
+
+
+def bitflip_decoder_type(weight=0.0):
+    """The result schema's decoder_type of a bit-flipping sweep: "bitflipping"
+    for weight == 0 (hard decisions only), else "bitflipping-gd"."""
+    return "bitflipping" if float(weight) == 0.0 else "bitflipping-gd"
+
+
+def check_decoder_args(decoder, bf_weight, bf_theta, mode, cn_rule="spa", schedule="flooding", qbits=None,
+                       layered_tile=False, quant_tile=False, nllr=False):
+    """ValueError for a decoder choice simulate() cannot honour (before any
+    device call): "bitflipping" needs mode="physical" and none of the
+    message-passing options; bf_weight / bf_theta need "bitflipping".  Returns
+    (weight, theta) as device.bitflip_args does."""
+    from .device import bitflip_args
+    if decoder not in DECODERS:
+        raise ValueError(f"decoder must be one of {DECODERS}, got {decoder!r}")
+    weight, theta = bitflip_args(bf_weight, bf_theta)
+    if decoder != "bitflipping":
+        if weight != 0.0 or theta != 0.0:
+            raise ValueError("bf_weight / bf_theta need decoder='bitflipping'")
+        return weight, theta
+    if mode != "physical":
+        raise ValueError("decoder='bitflipping' needs mode='physical' (parity mode is the reference's sum-product)")
+    if (cn_rule, schedule) != ("spa", "flooding") or qbits is not None or layered_tile or quant_tile or nllr:
+        raise ValueError("decoder='bitflipping' passes no messages: cn_rule, schedule, qbits, layered_tile, "
+                         "quant_tile and nllr do not apply to it")
+    return weight, theta
+
+
 def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65536, device=0,
              rank=0, world=1, allreduce=None, matrix_path="", mode="parity", cn_rule="spa", schedule="flooding",
              alpha=0.75, beta=0.5, qbits=None, llr_scale=4.0, layered_tile=False, quant_tile=False, stats=False,
-             max_failed=0, channel=None, snr_axis=None, rate_match=None):
+             max_failed=0, channel=None, snr_axis=None, rate_match=None, decoder="sumproduct", bf_weight=0.0,
+             bf_theta=0.0):
     """Full sweep on this process's GPU -> SimulationResult (reference schema).
 
     mode "parity" is the reference's decoder on H_std; "physical" decodes the
@@ -219,7 +251,15 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
     and shortens the frames; it needs mode="physical" and a channel model.  The
     Eb/N0 axis and the config's rate then use the effective rate
     (k - n_short) / E, the BER counts k - n_short information bits, and the
-    config's n, m, k stay the mother code's."""
+    config's n, m, k stay the mother code's.
+    decoder "bitflipping" (physical mode; the reference's --decoder value, which
+    it never dispatches) decodes the same frames by bit flipping with
+    bf_weight / bf_theta (device.bitflip_decode; Decoder.bitflip_mc_run); the
+    message-passing options must be at their defaults.  stats, channel,
+    snr_axis, rate_match and rank / world work as for the other decoders."""
+    bf_weight, bf_theta = check_decoder_args(decoder, bf_weight, bf_theta, mode, cn_rule, schedule, qbits,
+                                             layered_tile, quant_tile, nllr)
+    bf = (bf_weight, bf_theta) if decoder == "bitflipping" else None
     snr_axis = check_channel_args(channel, snr_axis, mode)
     rate_match = check_rate_match_args(rate_match, channel, mode)
     from .channel import sigmas_for_axis
@@ -244,7 +284,8 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
         from . import ira
         return _simulate_graph(getattr(ira, IRA_CODES[matrix])(), matrix, t0, snrs, blocks, max_iter, seed, chunk,
                                device, rank, world, allreduce, matrix_path, cn_rule, schedule, alpha, beta, qbits,
-                               llr_scale, layered_tile, quant_tile, stats, max_failed, channel, snr_axis, rate_match)
+                               llr_scale, layered_tile, quant_tile, stats, max_failed, channel, snr_axis, rate_match,
+                               bf)
     if isinstance(matrix, EncoderDecoderData):
         edd = matrix
     elif isinstance(matrix, str) and os.path.exists(matrix):
@@ -270,6 +311,8 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
         gp = Graph(edd.physical_matrix(), device=device)
 
         def counter_fn(sigmas, cnt, frame0):
+            if bf is not None:
+                return dec.bitflip_mc_run(gp, seed, sigmas, cnt, frame0, max_iter, weight=bf[0], theta=bf[1])
             return dec.phys_mc_run(gp, seed, sigmas, cnt, frame0, max_iter, cn=cn_rule, schedule=schedule,
                                    alpha=alpha, beta=beta, qbits=qbits, llr_scale=llr_scale, tile=layered_tile,
                                    qtile=quant_tile)
@@ -281,7 +324,9 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
     cfg = SimulationConfig(
         matrix_path=matrix_path or str(matrix), n=edd._n, m=edd._m, k=edd._k, rate=rate,
         blocks=int(blocks), max_iterations=int(max_iter), encoding_method="standard",
-        interleaver_type="none", decoder_type=decoder_type(cn_rule, schedule, qbits), channel_mode=1, modulation=1,
+        interleaver_type="none",
+        decoder_type=bitflip_decoder_type(bf[0]) if bf is not None else decoder_type(cn_rule, schedule, qbits),
+        channel_mode=1, modulation=1,
         speed=1.0, snr_range=(snrs[0], snrs[-1], (snrs[1] - snrs[0]) if len(snrs) > 1 else 0.0),
         threads=world, timestamp=datetime.now().isoformat())
     res = SimulationResult(config=cfg, snr_points=pts, wall_clock_seconds=time.time() - t0)
@@ -357,9 +402,10 @@ def check_stats_args(stats, max_failed, mode, world):
 
 def _simulate_graph(H, name, t0, snrs, blocks, max_iter, seed, chunk, device, rank, world, allreduce, matrix_path,
                     cn_rule, schedule, alpha, beta, qbits, llr_scale, layered_tile, quant_tile=False, stats=False,
-                    max_failed=0, channel=None, snr_axis="reference", rate_match=None):
+                    max_failed=0, channel=None, snr_axis="reference", rate_match=None, bf=None):
     """simulate() in physical mode on an IRA graph H: one graph, the decoder's
-    frame source and the graph it decodes on (as bench.py's config 5)."""
+    frame source and the graph it decodes on (as bench.py's config 5).
+    bf: (weight, theta) of the bit-flipping decoder, None for the others."""
     from .device import Decoder, Graph
     m, n = H.shape
     k = n - m
@@ -378,6 +424,8 @@ def _simulate_graph(H, name, t0, snrs, blocks, max_iter, seed, chunk, device, ra
         dec.set_rate_match(rate_match)
 
     def counter_fn(sigmas, cnt, frame0):
+        if bf is not None:
+            return dec.bitflip_mc_run(g, seed, sigmas, cnt, frame0, max_iter, weight=bf[0], theta=bf[1])
         return dec.phys_mc_run(g, seed, sigmas, cnt, frame0, max_iter, cn=cn_rule, schedule=schedule, alpha=alpha,
                                beta=beta, qbits=qbits, llr_scale=llr_scale, tile=layered_tile, qtile=quant_tile)
     if stats:
@@ -390,7 +438,8 @@ def _simulate_graph(H, name, t0, snrs, blocks, max_iter, seed, chunk, device, ra
     cfg = SimulationConfig(
         matrix_path=matrix_path or name, n=n, m=m, k=k, rate=rate, blocks=int(blocks),
         max_iterations=int(max_iter), encoding_method="standard", interleaver_type="none",
-        decoder_type=decoder_type(cn_rule, schedule, qbits), channel_mode=1, modulation=1, speed=1.0,
+        decoder_type=bitflip_decoder_type(bf[0]) if bf is not None else decoder_type(cn_rule, schedule, qbits),
+        channel_mode=1, modulation=1, speed=1.0,
         snr_range=(snrs[0], snrs[-1], (snrs[1] - snrs[0]) if len(snrs) > 1 else 0.0), threads=world,
         timestamp=datetime.now().isoformat())
     res = SimulationResult(config=cfg, snr_points=pts, wall_clock_seconds=time.time() - t0)
@@ -426,6 +475,13 @@ def build_parser():
                     help="with --qbits: quantizer steps per unit of LLR (default 4)")
     ap.add_argument("--quant-tile", action="store_true",
                     help="with --qbits: the HBM tile kernels even where the quantized state fits LDS")
+    ap.add_argument("--decoder", choices=DECODERS, default="sumproduct",
+                    help="the reference's flag: bitflipping (physical mode) is parallel gradient-descent bit flipping, "
+                         "the hard-decision baseline")
+    ap.add_argument("--bf-weight", type=float, default=None,
+                    help="with --decoder bitflipping: weight of the channel term, >= 0 (default 0: hard decisions only)")
+    ap.add_argument("--bf-theta", type=float, default=None,
+                    help="with --decoder bitflipping: flip where the inversion function is below this (default 0)")
     ap.add_argument("--stats-json", default=None, metavar="PATH",
                     help="physical mode: write the per-point Monte-Carlo statistics (convergence histogram, "
                          "FER by iteration limit, undetected errors, failed frames) to PATH")
@@ -472,6 +528,18 @@ def parse_args(argv=None):
         ap.error("--quant-tile needs --mode physical --qbits")
     if a.mode != "physical" and (a.stats_json is not None or a.max_failed != 0):
         ap.error("--stats-json and --max-failed need --mode physical")
+    if a.decoder != "bitflipping" and (a.bf_weight is not None or a.bf_theta is not None):
+        ap.error("--bf-weight and --bf-theta need --decoder bitflipping")
+    if a.decoder == "bitflipping":
+        if a.mode != "physical":
+            ap.error("--decoder bitflipping needs --mode physical")
+        if (a.cn_rule != "spa" or a.schedule != "flooding" or a.alpha is not None or a.beta is not None
+                or a.qbits is not None or a.llr_scale is not None or a.layered_tile or a.quant_tile
+                or a.normalized_llr):
+            ap.error("--decoder bitflipping passes no messages: --cn-rule, --schedule, --alpha, --beta, --qbits, "
+                     "--llr-scale, --layered-tile, --quant-tile and --normalized-llr do not apply to it")
+    a.bf_weight = 0.0 if a.bf_weight is None else a.bf_weight
+    a.bf_theta = 0.0 if a.bf_theta is None else a.bf_theta
     if a.max_failed != 0 and a.stats_json is None:
         ap.error("--max-failed needs --stats-json")
     if a.max_failed < 0:
@@ -485,6 +553,7 @@ def parse_args(argv=None):
         a.channel_spec = ChannelSpec(a.channel, a.modulation, a.demap)
         a.snr_axis = check_channel_args(a.channel_spec, a.snr_axis, a.mode)
         check_ira_mode(a.matrix, a.mode)
+        check_decoder_args(a.decoder, a.bf_weight, a.bf_theta, a.mode)
         phys_flags(tile=a.layered_tile, schedule=a.schedule)
         phys_rule_args(a.cn_rule, a.schedule, a.alpha, a.beta)
         if a.qbits is not None:
@@ -546,7 +615,8 @@ def main(argv=None):
                    device=local, rank=rank, world=world, allreduce=allreduce, mode=a.mode, cn_rule=a.cn_rule,
                    schedule=a.schedule, alpha=a.alpha, beta=a.beta, qbits=a.qbits, llr_scale=a.llr_scale,
                    layered_tile=a.layered_tile, quant_tile=a.quant_tile, stats=a.stats_json is not None,
-                   max_failed=a.max_failed, channel=a.channel_spec, snr_axis=a.snr_axis, rate_match=rate_match)
+                   max_failed=a.max_failed, channel=a.channel_spec, snr_axis=a.snr_axis, rate_match=rate_match,
+                   decoder=a.decoder, bf_weight=a.bf_weight, bf_theta=a.bf_theta)
     res = out[0]
     info = channel_info(a.channel_spec, a.snr_axis, snrs, res.config.rate, rate_match, res.config.n, res.config.k)
     if rank == 0 and a.stats_json is not None:

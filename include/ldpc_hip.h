@@ -627,6 +627,53 @@ int ldpc_rate_match_set(ldpc_decoder *d, int32_t n_punct, const int32_t *punct_c
 int ldpc_rate_match_get(const ldpc_decoder *d, int32_t *n_punct, int32_t *n_short,
                         int32_t *punct_out, int32_t punct_cap, int32_t *short_out, int32_t short_cap);
 
+/* -------------------- bit interleaver and block fading (physical mode only)
+ * Two more properties of the frame source, set as the channel and the pattern
+ * are and independent of them (new symbols under ABI 5: an addition only, the
+ * version stays 5).  No decoder kernel knows of either; they only change the
+ * frames of ldpc_generate_frames, ldpc_phys_mc_run, _ex, _q and ldpc_bf_mc_run.
+ * Interleaver: let tx[0 .. E-1] be the transmitted columns in ascending order;
+ * with no rate-matching pattern this is every column and E = n.  perm is a
+ * permutation pi of 0 .. E-1, read-from: transmitted position t carries column
+ * col(t) = tx[pi[t]].  Everything the channel-model and rate-matching contracts
+ * say of "transmitted position t" holds with col(t) in place of tx[t]: symbol s
+ * carries the positions s*bps .. s*bps + bps - 1, takes the noise pair of
+ * counter word s and the fade of index s; BPSK position t takes element t&1 of
+ * noise pair t>>1; the LLR of position t is written to column col(t) -- writing
+ * it there is the de-interleaving, so the decoders see the frame in column
+ * order as always.  The columns not sent, the info bits, the parities, the
+ * shortening, the counters, the statistics and the regeneration of a
+ * failed-frame record are unchanged.  The identity gives the frames of no
+ * interleaver.  The permutation is fixed until it is set again (one pattern for
+ * a run, as in a real link).
+ * Example: n = 6, no pattern, pi = {0, 3, 1, 4, 2, 5} (a block interleaver of 2
+ * rows, written by rows and read by columns), QPSK: symbol 0 carries the
+ * columns 0 and 3, symbol 1 carries 1 and 4, symbol 2 carries 2 and 5.
+ * Block fading (LDPC_CH_RAYLEIGH): with block_len = L the fade of symbol s
+ * (BPSK: of transmitted position t) is the fade of index B = floor(s / L)
+ * (floor(t / L)) under the channel model's draw: counter {F lo, F hi,
+ * 0x80000000 | (B>>1), (p<<1)|1}, u = the 52-bit uniform of words (0,1) for
+ * even B, of (2,3) for odd B, h = sqrt(-log u).  L = 1 (the default) is the
+ * channel-model section's channel, bit for bit; L >= the number of symbols is
+ * one fade per frame (quasi-static); the last block may be ragged.  The noise
+ * draws do not change.
+ * Both setters do no device work; the composite table col[] is uploaded by the
+ * first run that needs it, into the block the rate-matching tables use.
+ * ldpc_interleaver_set copies perm; len == 0 (perm may be NULL) clears it.
+ * LDPC_EINVAL, and the earlier setting stays in force, for: a NULL decoder;
+ * len < 0; NULL perm with len > 0; an entry outside [0, len); a duplicate
+ * entry; block_len < 1; for ldpc_interleaver_get a capacity too small for the
+ * stored permutation (perm_out == NULL only asks for the length).
+ * LDPC_EINVAL when frames are to be generated, before any device work, with a
+ * message that names the setting and how to clear it: an interleaver under the
+ * reference channel; len != E of the pattern set at that time; block_len > 1
+ * with a model other than LDPC_CH_RAYLEIGH.  The parity-mode ldpc_mc_run and
+ * ldpc_frame_order are LDPC_EINVAL while either setting is active. */
+int ldpc_interleaver_set(ldpc_decoder *d, int32_t len, const int32_t *perm);
+int ldpc_interleaver_get(const ldpc_decoder *d, int32_t *len, int32_t *perm_out, int32_t cap);
+int ldpc_fading_set(ldpc_decoder *d, int32_t block_len);
+int ldpc_fading_get(const ldpc_decoder *d, int32_t *block_len);
+
 /* ------------------------------------------------ multi-GPU (RCCL, xGMI)
  * One process per GPU; frames are sharded by global index, so the only
  * exchange is ONE all-reduce of the int64 counter matrix per Monte-Carlo step

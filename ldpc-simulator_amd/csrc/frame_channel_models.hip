@@ -35,6 +35,9 @@
 // frame_model_rm_kernel / frame_model_rm_row_kernel over the E transmitted bits,
 // frame_fill_kernel / frame_fill_row_kernel write the columns not sent, and
 // frame_shorten_kernel clears the shortened info bits ahead of the parity stage.
+// A bit interleaver (ldpc_interleaver_set) is those kernels with a permuted
+// tx_col; alone it has nothing to fill.  Rayleigh with a coherence length
+// (ldpc_fading_set) is frame_model_bf_kernel / frame_model_bf_row_kernel.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -100,12 +103,15 @@ struct Unit {
 
 // llr[0 .. kBits) of unit i of frame F; a BPSK bit past n - 1 (odd n) gets 0.
 // BPSK is one real dimension with the levels +-1: the one-bit expression with d = 1.
-// RM (a rate-matching pattern): n is the number of transmitted bits E and bit t
-// of the sequence is column tx[t]; else bit t is column t and tx is not read.
-template <int BPS, int MODEL, int DEMAP, bool RM = false>
+// RM (a rate-matching pattern or a bit interleaver): n is the number of
+// transmitted bits E and position t of the sequence is column tx[t]; else
+// position t is column t and tx is not read.
+// BF (block fading, Rayleigh): the two axes (BPSK: two bits) fade by hb[0],
+// hb[1], the caller's; else a fade of its own per symbol (BPSK: per bit).
+template <int BPS, int MODEL, int DEMAP, bool RM = false, bool BF = false>
 __device__ __forceinline__ void unit_llr(const uint32_t *Ut, const uint32_t *Pt, const uint32_t *Wt, int k, int n,
                                          uint64_t seed, int64_t F, int snr_point, int i, double sigma, double *llr,
-                                         const int32_t *__restrict__ tx = nullptr) {
+                                         const int32_t *__restrict__ tx = nullptr, const double *hb = nullptr) {
     constexpr int M = Unit<BPS>::kAxisBits;
     constexpr int L = 1 << M;
     constexpr double d = BPS == 1   ? 1.0
@@ -118,7 +124,10 @@ __device__ __forceinline__ void unit_llr(const uint32_t *Ut, const uint32_t *Pt,
     double h[2] = {1.0, 1.0};
     if constexpr (MODEL == kChRayleigh) {
         double u[2];
-        if constexpr (BPS == 1) {
+        if constexpr (BF) {
+            h[0] = hb[0];
+            h[1] = hb[1];
+        } else if constexpr (BPS == 1) {
             fade_uniforms(seed, F, snr_point, i, u);
             h[0] = sqrt(-log(u[0]));
             h[1] = sqrt(-log(u[1]));
@@ -147,6 +156,33 @@ __device__ __forceinline__ void unit_llr(const uint32_t *Ut, const uint32_t *Pt,
             llr[q] = 2.0 * h[q] * d * r / s2;
         else
             axis_llr<M, DEMAP>(r, h[q], s2, llr + q * M);
+    }
+}
+
+// Block fading (ldpc_fading_set, Rayleigh): the fade of index B, the draw a
+// symbol of that index has without it.
+__device__ __forceinline__ double block_fade(uint64_t seed, int64_t F, int snr_point, int B) {
+    double u[2];
+    fade_uniforms(seed, F, snr_point, B >> 1, u);
+    return sqrt(-log((B & 1) ? u[1] : u[0]));
+}
+
+// h[0], h[1] of unit i when block_len symbols (BPSK: transmitted positions)
+// share a fade: a symbol's two axes have index i / block_len, the two BPSK
+// positions 2i and 2i + 1 an index each.  {*Bc, *hc} is the caller's last
+// index and its fade (start with *Bc = -1): a caller that walks consecutive
+// units pays the log and sqrt once per fading block.
+template <int BPS>
+__device__ __forceinline__ void block_fades(uint64_t seed, int64_t F, int snr_point, int i, int block_len, int *Bc,
+                                            double *hc, double h[2]) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const int B = BPS == 1 ? (2 * i + q) / block_len : i / block_len;
+        if (B != *Bc) {
+            *Bc = B;
+            *hc = block_fade(seed, F, snr_point, B);
+        }
+        h[q] = *hc;
     }
 }
 
@@ -298,6 +334,96 @@ __global__ __launch_bounds__(64) void frame_model_rm_row_kernel(DevGraph g, DevS
     }
 }
 
+// ------------------------------------------------------------ block fading
+// Rayleigh with a coherence length (include/ldpc_hip.h "bit interleaver and
+// block fading", ch.fade_block > 1): instantiations of their own again, so that
+// with a fade per symbol the kernels above run exactly as they always did.  RM
+// as unit_llr's: the E positions of rm.tx_col, else the n columns in
+// order (rm is not read).  The tile form's workgroup walks consecutive units,
+// so it takes log and sqrt once per fading block it meets (a wave-uniform
+// branch: lanes are frames); a lane of the row form has one unit and one or
+// two fades.
+template <int BPS, int DEMAP, bool RM>
+__global__ __launch_bounds__(64) void frame_model_bf_kernel(DevGraph g, DevState st, PhysTile pt, RateMatchDev rm,
+                                                          uint64_t seed, int snr_point, double sigma, int64_t frame0,
+                                                          int to_lambda, int block_len) {
+    using U = Unit<BPS>;
+    const int kw = (g.k + 31) >> 5;
+    const int mw = (g.m + 31) >> 5;
+    const int mw32 = (mw + 31) >> 5;
+    const int nbits = RM ? rm.E : g.n;
+    const int units = U::count(nbits);
+    const int per_tile = (units + U::kPerBlock - 1) / U::kPerBlock;
+    const int tile = blockIdx.x / per_tile;
+    const int i0 = (blockIdx.x % per_tile) * U::kPerBlock;
+    const int i1 = min(units, i0 + U::kPerBlock);
+    const int lane = threadIdx.x;
+    const int f = tile * kTile + lane;
+    const bool valid = f < st.count;
+    const int64_t F = frame0 + f;
+    const uint32_t *Ut = st.ubits + (size_t)tile * kw * kTile + lane;
+    const uint32_t *Pt = pt.pbits + (size_t)tile * mw * kTile + lane;
+    const uint32_t *Wt = pt.wpar + (size_t)tile * mw32 * kTile + lane;
+    double *Ct = st.ch + (size_t)tile * g.n * kTile + lane;
+    float *Lamt = pt.Lam + (size_t)tile * g.n * kTile + lane;
+    float *Lt = pt.L + (size_t)tile * g.n * kTile + lane;
+    int Bc = -1;
+    double hc = 1.0;
+    for (int i = i0; i < i1; ++i) {
+        double h[2], llr[U::kBits];
+        block_fades<BPS>(seed, F, snr_point, i, block_len, &Bc, &hc, h);
+        unit_llr<BPS, kChRayleigh, DEMAP, RM, true>(Ut, Pt, Wt, g.k, nbits, seed, F, snr_point, i, sigma, llr, rm.tx_col,
+                                                    h);
+#pragma unroll
+        for (int t = 0; t < U::kBits; ++t) {
+            const int tb = i * U::kBits + t;
+            if (tb >= nbits) break;
+            const int j = RM ? rm.tx_col[tb] : tb;
+            const double v = valid ? llr[t] : 0.0;
+            if (to_lambda) {
+                Lamt[j * kTile] = -(float)v;
+                Lt[j * kTile] = -(float)v;
+            } else {
+                Ct[j * kTile] = v;
+            }
+        }
+    }
+}
+
+template <int BPS, int DEMAP, bool RM>
+__global__ __launch_bounds__(64) void frame_model_bf_row_kernel(DevGraph g, DevState st, PhysTile pt, RateMatchDev rm,
+                                                              uint64_t seed, int snr_point, double sigma,
+                                                              int64_t frame0, float *__restrict__ row_out,
+                                                              int block_len) {
+    using U = Unit<BPS>;
+    const int kw = (g.k + 31) >> 5;
+    const int mw = (g.m + 31) >> 5;
+    const int mw32 = (mw + 31) >> 5;
+    const int nbits = RM ? rm.E : g.n;
+    const int units = U::count(nbits);
+    const int per_frame = (units + 63) >> 6;
+    const int f = blockIdx.x / per_frame;
+    const int i = (blockIdx.x % per_frame) * 64 + threadIdx.x;
+    if (f >= st.count || i >= units) return;
+    const int tile = f >> 6, lf = f & 63;
+    const uint32_t *Ut = st.ubits + (size_t)tile * kw * kTile + lf;
+    const uint32_t *Pt = pt.pbits + (size_t)tile * mw * kTile + lf;
+    const uint32_t *Wt = pt.wpar + (size_t)tile * mw32 * kTile + lf;
+    int Bc = -1;
+    double hc = 1.0;
+    double h[2], llr[U::kBits];
+    block_fades<BPS>(seed, frame0 + f, snr_point, i, block_len, &Bc, &hc, h);
+    unit_llr<BPS, kChRayleigh, DEMAP, RM, true>(Ut, Pt, Wt, g.k, nbits, seed, frame0 + f, snr_point, i, sigma, llr,
+                                                rm.tx_col, h);
+    float *row = row_out + (size_t)f * g.n;
+#pragma unroll
+    for (int t = 0; t < U::kBits; ++t) {
+        const int tb = i * U::kBits + t;
+        if (tb >= nbits) break;
+        row[RM ? rm.tx_col[tb] : tb] = -(float)llr[t];
+    }
+}
+
 // The columns a pattern does not send, tile forms: lane = frame, a block walks
 // up to 128 of them; every store is 64 consecutive frames.  The value is the
 // column's LLR (+0.0 punctured, -LDPC_RM_KNOWN_LLR shortened), through the same
@@ -351,6 +477,20 @@ __global__ __launch_bounds__(64) void frame_shorten_kernel(DevGraph g, DevState 
     }
 }
 
+// The columns not sent, after the transmitted ones; an interleaver without a
+// pattern has none (n_fill == 0) and launches nothing.
+hipError_t launch_fill(const DevGraph &g, const DevState &st, const PhysTile &pt, const RateMatchDev &rm, FramesOut out,
+                       float *row_out, hipStream_t s) {
+    if (rm.n_fill > 0) {
+        if (out == kFramesRowLambda)
+            frame_fill_row_kernel<<<st.count * ((rm.n_fill + 63) >> 6), 64, 0, s>>>(g, st, rm, row_out);
+        else
+            frame_fill_kernel<<<st.ntiles * ((rm.n_fill + kFillPerBlock - 1) / kFillPerBlock), 64, 0, s>>>(
+                g, st, pt, rm, out == kFramesTileLambda ? 1 : 0);
+    }
+    return hipGetLastError();
+}
+
 template <int BPS, int MODEL, int DEMAP>
 hipError_t launch_model_rm(const DevGraph &g, const DevState &st, const PhysTile &pt, const RateMatchDev &rm,
                            uint64_t seed, int snr_point, double sigma, int64_t frame0, FramesOut out, float *row_out,
@@ -360,16 +500,48 @@ hipError_t launch_model_rm(const DevGraph &g, const DevState &st, const PhysTile
     if (out == kFramesRowLambda) {
         frame_model_rm_row_kernel<BPS, MODEL, DEMAP><<<st.count * ((units + 63) >> 6), 64, 0, s>>>(
             g, st, pt, rm, seed, snr_point, sigma, frame0, row_out);
-        frame_fill_row_kernel<<<st.count * ((rm.n_fill + 63) >> 6), 64, 0, s>>>(g, st, rm, row_out);
     } else {
         const int to_lambda = out == kFramesTileLambda ? 1 : 0;
         frame_model_rm_kernel<BPS, MODEL, DEMAP>
             <<<st.ntiles * ((units + U::kPerBlock - 1) / U::kPerBlock), 64, 0, s>>>(g, st, pt, rm, seed, snr_point,
                                                                                   sigma, frame0, to_lambda);
-        frame_fill_kernel<<<st.ntiles * ((rm.n_fill + kFillPerBlock - 1) / kFillPerBlock), 64, 0, s>>>(g, st, pt, rm,
-                                                                                                    to_lambda);
     }
-    return hipGetLastError();
+    return launch_fill(g, st, pt, rm, out, row_out, s);
+}
+
+// Rayleigh with ch.fade_block > 1; rm.E > 0: under a pattern and / or an interleaver.
+template <int BPS, int DEMAP, bool RM>
+hipError_t launch_model_bf(const DevGraph &g, const DevState &st, const PhysTile &pt, const RateMatchDev &rm,
+                           uint64_t seed, int snr_point, double sigma, int64_t frame0, FramesOut out, float *row_out,
+                           int block_len, hipStream_t s) {
+    using U = Unit<BPS>;
+    const int units = U::count(RM ? rm.E : g.n);
+    if (out == kFramesRowLambda)
+        frame_model_bf_row_kernel<BPS, DEMAP, RM><<<st.count * ((units + 63) >> 6), 64, 0, s>>>(
+            g, st, pt, rm, seed, snr_point, sigma, frame0, row_out, block_len);
+    else
+        frame_model_bf_kernel<BPS, DEMAP, RM><<<st.ntiles * ((units + U::kPerBlock - 1) / U::kPerBlock), 64, 0, s>>>(
+            g, st, pt, rm, seed, snr_point, sigma, frame0, out == kFramesTileLambda ? 1 : 0, block_len);
+    return RM ? launch_fill(g, st, pt, rm, out, row_out, s) : hipGetLastError();
+}
+
+template <bool RM>
+hipError_t launch_model_bf_of(const DevGraph &g, const DevState &st, const PhysTile &pt, const RateMatchDev &rm,
+                              uint64_t seed, int snr_point, double sigma, int64_t frame0, FramesOut out,
+                              float *row_out, const FrameChannel &ch, hipStream_t s) {
+    const bool maxlog = ch.demap == kDemapMaxlog;
+    const int bl = ch.fade_block;
+    switch (ch.bps) {
+        case 1: return launch_model_bf<1, 0, RM>(g, st, pt, rm, seed, snr_point, sigma, frame0, out, row_out, bl, s);
+        case 2: return launch_model_bf<2, 0, RM>(g, st, pt, rm, seed, snr_point, sigma, frame0, out, row_out, bl, s);
+        case 4:
+            return maxlog ? launch_model_bf<4, 1, RM>(g, st, pt, rm, seed, snr_point, sigma, frame0, out, row_out, bl, s)
+                          : launch_model_bf<4, 0, RM>(g, st, pt, rm, seed, snr_point, sigma, frame0, out, row_out, bl, s);
+        case 6:
+            return maxlog ? launch_model_bf<6, 1, RM>(g, st, pt, rm, seed, snr_point, sigma, frame0, out, row_out, bl, s)
+                          : launch_model_bf<6, 0, RM>(g, st, pt, rm, seed, snr_point, sigma, frame0, out, row_out, bl, s);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 template <int MODEL>
@@ -429,6 +601,9 @@ hipError_t launch_frame_channel_model(const DevGraph &g, const DevState &st, con
                                       int snr_point, double sigma, int64_t frame0, FramesOut out, float *row_out,
                                       const FrameChannel &ch, hipStream_t s) {
     if (ch.bps < 1 || g.n % ch.bps != 0 || st.count <= 0) return hipErrorInvalidValue;
+    if (ch.fade_block < 1 || (ch.fade_block > 1 && ch.model != kChRayleigh)) return hipErrorInvalidValue;
+    if (ch.fade_block > 1)
+        return launch_model_bf_of<false>(g, st, pt, RateMatchDev{}, seed, snr_point, sigma, frame0, out, row_out, ch, s);
     if (ch.model == kChRayleigh)
         return launch_model_of<kChRayleigh>(g, st, pt, seed, snr_point, sigma, frame0, out, row_out, ch, s);
     if (ch.model == 1)  // LDPC_CH_AWGN
@@ -440,9 +615,13 @@ hipError_t launch_frame_channel_model_rm(const DevGraph &g, const DevState &st, 
                                          int snr_point, double sigma, int64_t frame0, FramesOut out, float *row_out,
                                          const FrameChannel &ch, const RateMatchDev &rm, hipStream_t s) {
     if (ch.bps < 1 || st.count <= 0) return hipErrorInvalidValue;
-    if (rm.n_fill < 1 || rm.E < 1 || rm.E + rm.n_fill != g.n || rm.E % ch.bps != 0 || !rm.tx_col || !rm.fill_col ||
-        !rm.fill_llr)
+    // n_fill == 0: a bit interleaver without a pattern (no fill kernel runs)
+    if (rm.n_fill < 0 || rm.E < 1 || rm.E + rm.n_fill != g.n || rm.E % ch.bps != 0 || !rm.tx_col ||
+        (rm.n_fill > 0 && (!rm.fill_col || !rm.fill_llr)))
         return hipErrorInvalidValue;
+    if (ch.fade_block < 1 || (ch.fade_block > 1 && ch.model != kChRayleigh)) return hipErrorInvalidValue;
+    if (ch.fade_block > 1)
+        return launch_model_bf_of<true>(g, st, pt, rm, seed, snr_point, sigma, frame0, out, row_out, ch, s);
     if (ch.model == kChRayleigh)
         return launch_model_rm_of<kChRayleigh>(g, st, pt, rm, seed, snr_point, sigma, frame0, out, row_out, ch, s);
     if (ch.model == 1)  // LDPC_CH_AWGN

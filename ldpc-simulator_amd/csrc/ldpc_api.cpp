@@ -127,7 +127,10 @@ struct ldpc_decoder {
     std::vector<int32_t> rm_punct, rm_short;
     ldpc::RateMatchTables rm_tab;  // what rm_dev holds (or is about to)
     uint32_t *rm_dev = nullptr;    // rate_match_max_words(n, k) words, allocated once
-    bool rm_stale = false;         // the pattern changed since rm_dev was written
+    bool rm_stale = false;         // the pattern or the interleaver changed since rm_dev was written
+    // the frame source's bit interleaver (ldpc_interleaver_set): transmitted position t carries column
+    // tx[il_perm[t]]; empty: none.  The coherence length (ldpc_fading_set) is chan.fade_block.
+    std::vector<int32_t> il_perm;
     // profiling (ldpc_profile_*)
     bool prof = false;
     struct Span {
@@ -311,8 +314,20 @@ int channel_frames_check(const char *fn, const ldpc_decoder *d, uint32_t flags) 
     if (n_fill > 0 && d->chan.model == LDPC_CH_REFERENCE)
         return ldpc_fail(LDPC_EINVAL, "%s: a rate-matching pattern (ldpc_rate_match_set) needs a channel model, this "
                                       "decoder has the reference channel (ldpc_channel_set)", fn);
-    if (d->chan.model == LDPC_CH_REFERENCE) return LDPC_OK;
     const int n = d->g->dg.n;
+    if (!d->il_perm.empty() && d->chan.model == LDPC_CH_REFERENCE)
+        return ldpc_fail(LDPC_EINVAL, "%s: a bit interleaver (ldpc_interleaver_set) needs a channel model, this decoder "
+                                      "has the reference channel (ldpc_channel_set; ldpc_interleaver_set(d, 0, NULL) "
+                                      "clears the interleaver)", fn);
+    if (!d->il_perm.empty() && (int)d->il_perm.size() != n - n_fill)
+        return ldpc_fail(LDPC_EINVAL, "%s: the bit interleaver (ldpc_interleaver_set) has length %d, the pattern now set "
+                                      "transmits E = %d bits (ldpc_interleaver_set(d, 0, NULL) clears the interleaver)",
+                         fn, (int)d->il_perm.size(), n - n_fill);
+    if (d->chan.fade_block > 1 && d->chan.model != LDPC_CH_RAYLEIGH)
+        return ldpc_fail(LDPC_EINVAL, "%s: block fading (ldpc_fading_set, block_len = %d) needs LDPC_CH_RAYLEIGH, this "
+                                      "decoder's channel model is %d (ldpc_fading_set(d, 1) clears it)", fn,
+                         d->chan.fade_block, d->chan.model);
+    if (d->chan.model == LDPC_CH_REFERENCE) return LDPC_OK;
     if (n_fill > 0 && (n - n_fill) % d->chan.bps != 0)
         return ldpc_fail(LDPC_EINVAL, "%s: E = %d transmitted bits (n = %d less %d punctured and %d shortened) is not a "
                                       "multiple of bps = %d (the channel's bits per symbol)", fn, n - n_fill, n,
@@ -331,25 +346,38 @@ int channel_parity_check(const char *fn, const ldpc_decoder *d) {
     if (!d->rm_punct.empty() || !d->rm_short.empty())
         return ldpc_fail(LDPC_EINVAL, "%s: parity mode sends every code whole; rate matching is physical mode's "
                                       "(ldpc_rate_match_set(d, 0, NULL, 0, NULL) clears the pattern)", fn);
+    if (!d->il_perm.empty())
+        return ldpc_fail(LDPC_EINVAL, "%s: parity mode sends every code in column order; the bit interleaver is physical "
+                                      "mode's (ldpc_interleaver_set(d, 0, NULL) clears it)", fn);
+    if (d->chan.fade_block > 1)
+        return ldpc_fail(LDPC_EINVAL, "%s: parity mode has the reference channel only; block fading is physical mode's "
+                                      "(ldpc_fading_set(d, 1) clears it)", fn);
     if (d->chan.model == LDPC_CH_REFERENCE) return LDPC_OK;
     return ldpc_fail(LDPC_EINVAL, "%s: parity mode has the reference channel only; the channel models are physical "
                                   "mode's (ldpc_channel_set(d, NULL) puts the reference channel back)", fn);
 }
 
-// The decoder's rate-matching pattern for the frame source's kernels: nothing
-// (n_fill = 0) without one, else its tables in device memory, uploaded on
-// stream s if the pattern changed since they were (a copy from pageable host
+// The decoder's rate-matching pattern and bit interleaver for the frame source's
+// kernels: nothing (E = 0) without either, else their tables in device memory
+// (tx_col the composite tx[perm[t]]), built, checked and uploaded on stream s
+// if either changed since they were (a copy from pageable host
 // memory: rm_tab has been read when hipMemcpyAsync returns).
 int rate_match_dev(ldpc_decoder *d, hipStream_t s, ldpc::RateMatchDev *out) {
     *out = ldpc::RateMatchDev{};
-    if (d->rm_punct.empty() && d->rm_short.empty()) return LDPC_OK;
+    if (d->rm_punct.empty() && d->rm_short.empty() && d->il_perm.empty()) return LDPC_OK;
     const DevGraph &G = d->g->dg;
     if (!d->rm_dev) {
         if (int rc = dev_alloc(&d->rm_dev, ldpc::rate_match_max_words(G.n, G.k))) return rc;
         d->rm_stale = true;
     }
     if (d->rm_stale) {
-        d->rm_tab = ldpc::rate_match_build(G.n, G.k, d->rm_punct, d->rm_short);
+        // an interleaver alone: E = n, no fill lists, an all-ones mask; tx_col becomes tx[perm[t]]
+        ldpc::RateMatchTables tab = ldpc::rate_match_build(G.n, G.k, d->rm_punct, d->rm_short);
+        if ((!d->il_perm.empty() && !ldpc::interleaver_apply(tab, d->il_perm)) ||
+            !ldpc::rate_match_tables_ok(tab, G.n, G.k))
+            return ldpc_fail(LDPC_EINVAL, "the frame source's tables do not fit the code: interleaver length %d, E = %d",
+                             (int)d->il_perm.size(), tab.E);
+        d->rm_tab = std::move(tab);
         HIP_TRY(hipMemcpyAsync(d->rm_dev, d->rm_tab.words.data(), sizeof(uint32_t) * d->rm_tab.words.size(),
                                hipMemcpyHostToDevice, s));
         d->rm_stale = false;
@@ -2489,6 +2517,7 @@ int ldpc_channel_set(ldpc_decoder *d, const ldpc_channel *ch) {
         c.demap = ch->demap;
     }
     if (!d) return ldpc_fail(LDPC_EINVAL, "%s: NULL decoder", fn);
+    c.fade_block = d->chan.fade_block;  // ldpc_fading_set's, a setting of its own
     d->chan = c;
     return LDPC_OK;
 }
@@ -2532,6 +2561,48 @@ int ldpc_rate_match_get(const ldpc_decoder *d, int32_t *n_punct, int32_t *n_shor
         if (punct_out) std::copy(d->rm_punct.begin(), d->rm_punct.end(), punct_out);
         if (short_out) std::copy(d->rm_short.begin(), d->rm_short.end(), short_out);
     }
+    return LDPC_OK;
+}
+
+// ------------------------------------- bit interleaver and block fading
+int ldpc_interleaver_set(ldpc_decoder *d, int32_t len, const int32_t *perm) {
+    const char *fn = "ldpc_interleaver_set";
+    if (!d) return ldpc_fail(LDPC_EINVAL, "%s: NULL decoder", fn);
+    const std::string err = ldpc::interleaver_validate(len, perm);
+    if (!err.empty()) return ldpc_fail(LDPC_EINVAL, "%s: %s", fn, err.c_str());
+    if (len > 0)
+        d->il_perm.assign(perm, perm + len);
+    else
+        d->il_perm.clear();
+    d->rm_stale = true;
+    return LDPC_OK;
+}
+
+int ldpc_interleaver_get(const ldpc_decoder *d, int32_t *len, int32_t *perm_out, int32_t cap) {
+    const char *fn = "ldpc_interleaver_get";
+    if (!d) return ldpc_fail(LDPC_EINVAL, "%s: NULL decoder", fn);
+    if (!len || cap < 0 || (cap > 0 && !perm_out)) return ldpc_fail(LDPC_EINVAL, "%s: bad arguments", fn);
+    *len = (int32_t)d->il_perm.size();
+    if (perm_out) {
+        if (cap < *len)
+            return ldpc_fail(LDPC_EINVAL, "%s: capacity %d is too small for a permutation of length %d", fn, cap, *len);
+        std::copy(d->il_perm.begin(), d->il_perm.end(), perm_out);
+    }
+    return LDPC_OK;
+}
+
+int ldpc_fading_set(ldpc_decoder *d, int32_t block_len) {
+    const char *fn = "ldpc_fading_set";
+    if (!d) return ldpc_fail(LDPC_EINVAL, "%s: NULL decoder", fn);
+    if (block_len < 1) return ldpc_fail(LDPC_EINVAL, "%s: block_len %d < 1 (1 is a fade per symbol)", fn, block_len);
+    d->chan.fade_block = block_len;
+    return LDPC_OK;
+}
+
+int ldpc_fading_get(const ldpc_decoder *d, int32_t *block_len) {
+    if (!d) return ldpc_fail(LDPC_EINVAL, "ldpc_fading_get: NULL decoder");
+    if (!block_len) return ldpc_fail(LDPC_EINVAL, "ldpc_fading_get: NULL block_len");
+    *block_len = d->chan.fade_block;
     return LDPC_OK;
 }
 

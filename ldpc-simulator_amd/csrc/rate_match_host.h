@@ -1,8 +1,10 @@
 // rate_match_host.h -- host side of the frame source's rate-matching pattern
 // (include/ldpc_hip.h "rate matching"): the validation of ldpc_rate_match_set
-// and the tables the kernels of frame_rate_match.hip read.  No HIP here, so a
-// stand-alone program can run it under a sanitizer
-// (tools/rate_match_host_check.cpp).
+// and the tables the kernels of frame_rate_match.hip read; and of its bit
+// interleaver ("bit interleaver and block fading"): the validation of
+// ldpc_interleaver_set and the composite table col[t] = tx[perm[t]].  No HIP
+// here, so a stand-alone program can run it under a sanitizer
+// (tools/rate_match_host_check.cpp, tools/interleave_host_check.cpp).
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -87,6 +89,54 @@ inline RateMatchTables rate_match_build(int n, int k, const std::vector<int32_t>
     for (int w = 0; w < t.kw; ++w) t.words[t.mask_off() + (size_t)w] = 0xFFFFFFFFu;
     for (int32_t c : shrt) t.words[t.mask_off() + (size_t)(c >> 5)] &= ~(1u << (c & 31));
     return t;
+}
+
+// ------------------------------------------------------------ interleaver
+// (include/ldpc_hip.h "bit interleaver and block fading")  Empty when perm is a
+// permutation of 0 .. len-1 (len == 0: none), else what is wrong with it.
+inline std::string interleaver_validate(int32_t len, const int32_t *perm) {
+    if (len < 0) return "negative length (len = " + std::to_string(len) + ")";
+    if (len > 0 && !perm) return "NULL perm with a positive length";
+    std::vector<uint8_t> seen((size_t)len, 0);
+    for (int32_t t = 0; t < len; ++t) {
+        const int32_t v = perm[t];
+        if (v < 0 || v >= len)
+            return "entry " + std::to_string(v) + " (position " + std::to_string(t) + ") is outside [0, " +
+                   std::to_string(len) + ")";
+        if (seen[(size_t)v]) return "entry " + std::to_string(v) + " is listed twice (duplicate)";
+        seen[(size_t)v] = 1;
+    }
+    return std::string();
+}
+
+// The composite table: tx_col[t] = tx[perm[t]] in place, so that transmitted
+// position t carries column tx[perm[t]].  perm must have passed
+// interleaver_validate; false (tables untouched) unless its length is t.E.
+inline bool interleaver_apply(RateMatchTables &t, const std::vector<int32_t> &perm) {
+    if ((int)perm.size() != t.E) return false;
+    std::vector<uint32_t> tx(t.words.begin() + (std::ptrdiff_t)t.tx_off(),
+                             t.words.begin() + (std::ptrdiff_t)(t.tx_off() + (size_t)t.E));
+    for (int i = 0; i < t.E; ++i) {
+        const int32_t p = perm[(size_t)i];
+        if (p < 0 || p >= t.E) return false;
+        t.words[t.tx_off() + (size_t)i] = tx[(size_t)p];
+    }
+    return true;
+}
+
+// The last gate before an upload: every index a kernel gathers or scatters with
+// lies in [0, n), tx_col and fill_col together name every column exactly once,
+// and the block fits the device allocation.
+inline bool rate_match_tables_ok(const RateMatchTables &t, int n, int k) {
+    if (t.E < 1 || t.n_fill < 0 || t.E + t.n_fill != n || t.kw != ((k + 31) >> 5)) return false;
+    if (t.words.size() != t.mask_off() + (size_t)t.kw || t.words.size() > rate_match_max_words(n, k)) return false;
+    std::vector<uint8_t> seen((size_t)n, 0);
+    for (size_t i = 0; i < (size_t)t.E + (size_t)t.n_fill; ++i) {
+        const uint32_t c = t.words[i];  // tx_col, then fill_col
+        if (c >= (uint32_t)n || seen[c]) return false;
+        seen[c] = 1;
+    }
+    return true;
 }
 
 }  // namespace ldpc

@@ -312,13 +312,16 @@ struct FrameChannel {
     int model = 0;
     int bps = 1;
     int demap = 0;
+    int fade_block = 1;  // Rayleigh: symbols (BPSK: bits) that share a fade (ldpc_fading_set); 1: a fade each
 };
 // A decoder's rate-matching pattern as the frame source's kernels read it
 // (include/ldpc_hip.h "rate matching"; tables built by rate_match_host.h, in
 // device memory the decoder owns).  Per decoder, so not in DevGraph: a graph is
-// shared.  The default (n_fill == 0) is no pattern: every column is sent.
+// shared.  The default (E == 0) is no tables: every column is sent, in column
+// order.  With a bit interleaver (ldpc_interleaver_set) tx_col is the composite
+// tx[perm[t]], and n_fill may be 0 (an interleaver without a pattern, E == n).
 struct RateMatchDev {
-    const int32_t *tx_col = nullptr;    // [E] transmitted columns, ascending
+    const int32_t *tx_col = nullptr;    // [E] the column of transmitted position t (ascending without an interleaver)
     const int32_t *fill_col = nullptr;  // [n_fill] the columns not sent
     const float *fill_llr = nullptr;    // [n_fill] their LLR: +0.0 punctured, -LDPC_RM_KNOWN_LLR shortened
     const uint32_t *umask = nullptr;    // [kw] AND mask of st.ubits (shortened bits clear)
@@ -333,8 +336,9 @@ hipError_t launch_frames(const DevGraph &g, const DevState &st, const PhysTile &
 hipError_t launch_frame_channel_model(const DevGraph &g, const DevState &st, const PhysTile &pt, uint64_t seed,
                                       int snr_point, double sigma, int64_t frame0, FramesOut out, float *row_out,
                                       const FrameChannel &ch, hipStream_t s);
-// The same under a rate-matching pattern (rm.n_fill > 0, rm.E % ch.bps == 0):
-// the transmitted columns' LLRs, then the fill of the others.
+// The same under a rate-matching pattern and / or a bit interleaver (rm.E > 0,
+// rm.E % ch.bps == 0): the transmitted columns' LLRs, then the fill of the
+// others if there are any (rm.n_fill > 0).
 hipError_t launch_frame_channel_model_rm(const DevGraph &g, const DevState &st, const PhysTile &pt, uint64_t seed,
                                          int snr_point, double sigma, int64_t frame0, FramesOut out, float *row_out,
                                          const FrameChannel &ch, const RateMatchDev &rm, hipStream_t s);

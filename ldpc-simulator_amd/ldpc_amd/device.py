@@ -413,6 +413,48 @@ class Decoder:
             self._h, ctypes.byref(npu), ctypes.byref(nsh), _lib.i32p(p), len(p), _lib.i32p(s), len(s)))
         return RateMatch(tuple(int(x) for x in p[:npu.value]), tuple(int(x) for x in s[:nsh.value]))
 
+    def set_interleaver(self, il):
+        """The frame source's bit interleaver for generate(), phys_mc_run() and
+        bitflip_mc_run() on this decoder from now on (ldpc_interleaver_set): an
+        interleave.Interleaver; None clears it.  Its length must be the E of the
+        pattern in force when frames are generated.  No device work."""
+        from .interleave import Interleaver
+        if il is None:
+            check("ldpc_interleaver_set", _lib.lib().ldpc_interleaver_set(self._h, 0, None))
+            return
+        if not isinstance(il, Interleaver):
+            raise ValueError(f"set_interleaver takes an Interleaver or None, got {type(il).__name__}")
+        p = _lib.as_i32(il.perm)
+        check("ldpc_interleaver_set", _lib.lib().ldpc_interleaver_set(self._h, len(p), _lib.i32p(p) if len(p) else None))
+
+    @property
+    def interleaver(self):
+        """The interleaver in force as an interleave.Interleaver (kind "custom":
+        the library keeps the permutation only), None without one."""
+        from .interleave import Interleaver
+        n = _lib.c_i32()
+        check("ldpc_interleaver_get", _lib.lib().ldpc_interleaver_get(self._h, ctypes.byref(n), None, 0))
+        if n.value == 0:
+            return None
+        p = np.zeros(n.value, np.int32)
+        check("ldpc_interleaver_get", _lib.lib().ldpc_interleaver_get(self._h, ctypes.byref(n), _lib.i32p(p), len(p)))
+        return Interleaver(tuple(int(x) for x in p))
+
+    def set_fading_block(self, block_len):
+        """The Rayleigh channel's coherence length from now on (ldpc_fading_set):
+        block_len symbols (BPSK: bits) share a fade; 1 is a fade each (the
+        default), anything >= the symbols of a frame is one fade per frame."""
+        if isinstance(block_len, bool) or int(block_len) != block_len or not 1 <= block_len <= 2 ** 31 - 1:
+            raise ValueError(f"set_fading_block takes an integer in [1, 2^31 - 1], got {block_len!r}")
+        check("ldpc_fading_set", _lib.lib().ldpc_fading_set(self._h, int(block_len)))
+
+    @property
+    def fading_block(self):
+        """The coherence length in force (ldpc_fading_get)."""
+        n = _lib.c_i32()
+        check("ldpc_fading_get", _lib.lib().ldpc_fading_get(self._h, ctypes.byref(n)))
+        return int(n.value)
+
     def generate(self, seed, snr_point, sigma, frame0, count, test_zero=False):
         """On-device synthetic frames (u bits, channel LLRs) copied back for testing.
         test_zero: the frame source's test-only erasures (LDPC_F_TEST_ZERO)."""

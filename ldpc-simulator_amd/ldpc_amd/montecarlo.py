@@ -222,7 +222,7 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
              rank=0, world=1, allreduce=None, matrix_path="", mode="parity", cn_rule="spa", schedule="flooding",
              alpha=0.75, beta=0.5, qbits=None, llr_scale=4.0, layered_tile=False, quant_tile=False, stats=False,
              max_failed=0, channel=None, snr_axis=None, rate_match=None, decoder="sumproduct", bf_weight=0.0,
-             bf_theta=0.0):
+             bf_theta=0.0, interleaver=None, fading_block=1):
     """Full sweep on this process's GPU -> SimulationResult (reference schema).
 
     mode "parity" is the reference's decoder on H_std; "physical" decodes the
@@ -256,12 +256,21 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
     it never dispatches) decodes the same frames by bit flipping with
     bf_weight / bf_theta (device.bitflip_decode; Decoder.bitflip_mc_run); the
     message-passing options must be at their defaults.  stats, channel,
-    snr_axis, rate_match and rank / world work as for the other decoders."""
+    snr_axis, rate_match and rank / world work as for the other decoders.
+    interleaver (an interleave.Interleaver, or one of its spec strings: none,
+    regular, block:R, random[:seed], srandom:S[:seed], file:PATH; None = the
+    frame's column order) permutes the transmitted bits before they are mapped
+    to symbols; a spec is resolved against E once the code and the pattern are
+    known.  It needs mode="physical" and a channel model.  fading_block (an
+    integer >= 1, or "frame") is the Rayleigh channel's coherence length in
+    symbols (BPSK: bits): 1 is a fade per symbol, "frame" one fade per frame;
+    anything but 1 needs channel model "rayleigh"."""
     bf_weight, bf_theta = check_decoder_args(decoder, bf_weight, bf_theta, mode, cn_rule, schedule, qbits,
                                              layered_tile, quant_tile, nllr)
     bf = (bf_weight, bf_theta) if decoder == "bitflipping" else None
     snr_axis = check_channel_args(channel, snr_axis, mode)
     rate_match = check_rate_match_args(rate_match, channel, mode)
+    interleaver, fading_block = check_interleave_args(interleaver, fading_block, channel, mode)
     from .channel import sigmas_for_axis
     from .code import EncoderDecoderData, load_committed_code
     from .device import Decoder, Graph, phys_flags, phys_quant_args, phys_rule_args
@@ -285,7 +294,7 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
         return _simulate_graph(getattr(ira, IRA_CODES[matrix])(), matrix, t0, snrs, blocks, max_iter, seed, chunk,
                                device, rank, world, allreduce, matrix_path, cn_rule, schedule, alpha, beta, qbits,
                                llr_scale, layered_tile, quant_tile, stats, max_failed, channel, snr_axis, rate_match,
-                               bf)
+                               bf, interleaver, fading_block)
     if isinstance(matrix, EncoderDecoderData):
         edd = matrix
     elif isinstance(matrix, str) and os.path.exists(matrix):
@@ -298,12 +307,15 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
         # ValueErrors before any device call
         sent, k_info, rate = rate_match_shape(rate_match, channel, edd._n, edd._k)
         channel.check_length(sent)
+        interleaver = resolve_interleaver(interleaver, sent)
         sigmas = sigmas_for_axis(channel, snr_axis, snrs, rate)
     g = Graph(edd._h_std, device=device)
     dec = Decoder(g, Decoder.fit_slots(g, min(max(1, shard(int(blocks), rank, world)[1]), chunk)))
     if sigmas is not None:
         dec.set_channel(channel)
         dec.set_rate_match(rate_match)
+        dec.set_interleaver(interleaver)
+        dec.set_fading_block(fading_block)
     counter_fn = None
     if stats:
         dec.mc_stats(True, max_failed)
@@ -324,7 +336,7 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
     cfg = SimulationConfig(
         matrix_path=matrix_path or str(matrix), n=edd._n, m=edd._m, k=edd._k, rate=rate,
         blocks=int(blocks), max_iterations=int(max_iter), encoding_method="standard",
-        interleaver_type="none",
+        interleaver_type=interleaver.kind if interleaver is not None else "none",
         decoder_type=bitflip_decoder_type(bf[0]) if bf is not None else decoder_type(cn_rule, schedule, qbits),
         channel_mode=1, modulation=1,
         speed=1.0, snr_range=(snrs[0], snrs[-1], (snrs[1] - snrs[0]) if len(snrs) > 1 else 0.0),
@@ -363,6 +375,57 @@ def check_rate_match_args(rate_match, channel, mode):
     return rate_match
 
 
+FADING_FRAME = 2 ** 31 - 1  # fading_block="frame": a coherence length no frame reaches
+
+
+def check_interleave_args(interleaver, fading_block, channel, mode):
+    """ValueError for an interleaver / coherence length simulate() cannot
+    honour (before any code is loaded); returns (interleaver, fading_block)
+    with "none" as None and "frame" as FADING_FRAME.  A spec string is checked
+    for its form here and resolved once E is known (resolve_interleaver)."""
+    from .interleave import Interleaver, split_spec
+    model = channel is not None and not channel.is_reference
+    if isinstance(interleaver, str):
+        if split_spec(interleaver)[0] == "none":
+            interleaver = None
+    elif interleaver is not None and not isinstance(interleaver, Interleaver):
+        raise ValueError(f"interleaver must be an Interleaver, a spec string or None, got {type(interleaver).__name__}")
+    if interleaver is not None:
+        if mode != "physical":
+            raise ValueError("interleaver needs mode='physical' (parity mode sends every code in column order)")
+        if not model:
+            raise ValueError("interleaver needs a channel model (channel=ChannelSpec('awgn' / 'rayleigh', ...)): it "
+                             "cannot change decoding on the memoryless reference channel")
+    if isinstance(fading_block, str):
+        if fading_block.strip().lower() != "frame":
+            raise ValueError(f"fading_block must be an integer >= 1 or 'frame', got {fading_block!r}")
+        fading_block = FADING_FRAME
+    if isinstance(fading_block, bool) or not isinstance(fading_block, int) or not 1 <= fading_block <= FADING_FRAME:
+        raise ValueError(f"fading_block must be an integer in [1, {FADING_FRAME}] or 'frame', got {fading_block!r}")
+    if fading_block > 1:
+        if mode != "physical":
+            raise ValueError("fading_block needs mode='physical'")
+        if not model or channel.model != "rayleigh":
+            raise ValueError("fading_block > 1 needs the Rayleigh channel (channel=ChannelSpec('rayleigh', ...)): "
+                             "no other model has a fade")
+    return interleaver, fading_block
+
+
+def resolve_interleaver(interleaver, E):
+    """The Interleaver of simulate()'s argument for E transmitted bits (None
+    without one); ValueError where the spec or the length does not fit."""
+    from .interleave import resolve
+    return resolve(interleaver, E)
+
+
+def interleave_header(info):
+    """The command line's header line of an interleaved / block-faded sweep."""
+    il = info.get("interleaver")
+    what = "none" if il is None else " ".join(f"{k} {v}" for k, v in il.items())
+    fb = info.get("fading_block", 1)
+    return f"interleaver {what}  coherence length {fb}" + ("" if fb == "frame" else " symbol(s)")
+
+
 def rate_match_shape(rate_match, channel, n, k):
     """(transmitted bits E, information bits, effective rate) of an (n, k) code
     under the pattern (None: n, k, k / n); ValueError for a pattern the code or
@@ -373,11 +436,13 @@ def rate_match_shape(rate_match, channel, n, k):
     return rate_match.n_transmitted(n), rate_match.info_bits(k), rate_match.effective_rate(n, k)
 
 
-def channel_info(channel, snr_axis, snrs, rate, rate_match=None, n=None, k=None):
+def channel_info(channel, snr_axis, snrs, rate, rate_match=None, n=None, k=None, interleaver=None, fading_block=1):
     """The sweep's channel as --stats-json writes it: model, modulation, demap,
     snr_axis and sigma per point; under a rate-matching pattern (then with the
     mother code's n and k, and `rate` the effective rate) also "rate_match":
-    the columns, the transmitted and information bits and the rate."""
+    the columns, the transmitted and information bits and the rate; with an
+    interleaver (an Interleaver) "interleaver": its info(); with a coherence
+    length other than 1 "fading_block" (FADING_FRAME as "frame")."""
     from .channel import ChannelSpec, resolve_snr_axis, sigmas_for_axis
     channel = channel or ChannelSpec()
     snr_axis = resolve_snr_axis(channel, snr_axis)
@@ -385,6 +450,10 @@ def channel_info(channel, snr_axis, snrs, rate, rate_match=None, n=None, k=None)
             "sigma": [float(x) for x in sigmas_for_axis(channel, snr_axis, snrs, rate)]}
     if rate_match is not None and not rate_match.is_empty:
         info["rate_match"] = rate_match.info(n, k)
+    if interleaver is not None:
+        info["interleaver"] = interleaver.info()
+    if fading_block != 1:
+        info["fading_block"] = "frame" if fading_block == FADING_FRAME else int(fading_block)
     return info
 
 
@@ -402,7 +471,8 @@ def check_stats_args(stats, max_failed, mode, world):
 
 def _simulate_graph(H, name, t0, snrs, blocks, max_iter, seed, chunk, device, rank, world, allreduce, matrix_path,
                     cn_rule, schedule, alpha, beta, qbits, llr_scale, layered_tile, quant_tile=False, stats=False,
-                    max_failed=0, channel=None, snr_axis="reference", rate_match=None, bf=None):
+                    max_failed=0, channel=None, snr_axis="reference", rate_match=None, bf=None, interleaver=None,
+                    fading_block=1):
     """simulate() in physical mode on an IRA graph H: one graph, the decoder's
     frame source and the graph it decodes on (as bench.py's config 5).
     bf: (weight, theta) of the bit-flipping decoder, None for the others."""
@@ -416,12 +486,15 @@ def _simulate_graph(H, name, t0, snrs, blocks, max_iter, seed, chunk, device, ra
         # ValueErrors before any device call
         sent, k_info, rate = rate_match_shape(rate_match, channel, n, k)
         channel.check_length(sent)
+        interleaver = resolve_interleaver(interleaver, sent)
         sigmas = sigmas_for_axis(channel, snr_axis, snrs, rate)
     g = Graph(H, device=device)
     dec = Decoder(g, Decoder.fit_slots(g, min(max(1, shard(int(blocks), rank, world)[1]), chunk)))
     if sigmas is not None:
         dec.set_channel(channel)
         dec.set_rate_match(rate_match)
+        dec.set_interleaver(interleaver)
+        dec.set_fading_block(fading_block)
 
     def counter_fn(sigmas, cnt, frame0):
         if bf is not None:
@@ -437,7 +510,8 @@ def _simulate_graph(H, name, t0, snrs, blocks, max_iter, seed, chunk, device, ra
     pts = point_results(ctr, k_info, snrs, matrix_path=matrix_path or name, max_iter=max_iter)
     cfg = SimulationConfig(
         matrix_path=matrix_path or name, n=n, m=m, k=k, rate=rate, blocks=int(blocks),
-        max_iterations=int(max_iter), encoding_method="standard", interleaver_type="none",
+        max_iterations=int(max_iter), encoding_method="standard",
+        interleaver_type=interleaver.kind if interleaver is not None else "none",
         decoder_type=bitflip_decoder_type(bf[0]) if bf is not None else decoder_type(cn_rule, schedule, qbits),
         channel_mode=1, modulation=1, speed=1.0,
         snr_range=(snrs[0], snrs[-1], (snrs[1] - snrs[0]) if len(snrs) > 1 else 0.0), threads=world,
@@ -503,6 +577,12 @@ def build_parser():
     ap.add_argument("--shorten", default=None, metavar="COLS",
                     help="with --channel awgn / rayleigh: information columns both ends know to be 0, not sent "
                          "(the same grammar, e.g. 0:24)")
+    ap.add_argument("--interleaver", default=None, metavar="SPEC",
+                    help="with --channel awgn / rayleigh: bit interleaver of the transmitted bits, fixed for the run: "
+                         "none, regular, block:R, random[:seed], srandom:S[:seed] or file:PATH")
+    ap.add_argument("--fading-block", default=None, metavar="L|frame",
+                    help="with --channel rayleigh: symbols (BPSK: bits) that share a fade (default 1); frame: one "
+                         "fade per frame")
     return ap
 
 
@@ -546,12 +626,23 @@ def parse_args(argv=None):
         ap.error("--max-failed must be >= 0")
     if (a.puncture is not None or a.shorten is not None) and (a.mode != "physical" or a.channel == "reference"):
         ap.error("--puncture and --shorten need --mode physical --channel awgn or rayleigh")
+    if a.interleaver is not None and (a.mode != "physical" or a.channel == "reference"):
+        ap.error("--interleaver needs --mode physical --channel awgn or rayleigh")
+    if a.fading_block is not None and (a.mode != "physical" or a.channel != "rayleigh"):
+        ap.error("--fading-block needs --mode physical --channel rayleigh")
+    if a.fading_block is not None and a.fading_block.strip().lower() != "frame":
+        try:
+            a.fading_block = int(a.fading_block)
+        except ValueError:
+            ap.error(f"--fading-block takes an integer >= 1 or 'frame', got {a.fading_block!r}")
+    a.fading_block = 1 if a.fading_block is None else a.fading_block
     a.llr_scale = 4.0 if a.llr_scale is None else a.llr_scale
     a.alpha = 0.75 if a.alpha is None else a.alpha
     a.beta = 0.5 if a.beta is None else a.beta
     try:
         a.channel_spec = ChannelSpec(a.channel, a.modulation, a.demap)
         a.snr_axis = check_channel_args(a.channel_spec, a.snr_axis, a.mode)
+        a.interleaver, a.fading_block = check_interleave_args(a.interleaver, a.fading_block, a.channel_spec, a.mode)
         check_ira_mode(a.matrix, a.mode)
         check_decoder_args(a.decoder, a.bf_weight, a.bf_theta, a.mode)
         phys_flags(tile=a.layered_tile, schedule=a.schedule)
@@ -611,14 +702,23 @@ def main(argv=None):
         rate_match = cli_rate_match(a)  # the code's n and k without a device
     except ValueError as e:
         raise SystemExit(f"--puncture / --shorten: {e}")
+    interleaver = a.interleaver
+    if interleaver is not None:
+        try:  # resolved here, without a device, so that the header and the JSON name what ran
+            n, k = code_shape(a.matrix)
+            interleaver = resolve_interleaver(interleaver, rate_match_shape(rate_match, a.channel_spec, n, k)[0])
+        except (ValueError, OSError) as e:
+            raise SystemExit(f"--interleaver: {e}")
     out = simulate(a.matrix, snrs, a.blocks, a.iterations, seed=a.seed, nllr=a.normalized_llr,
                    device=local, rank=rank, world=world, allreduce=allreduce, mode=a.mode, cn_rule=a.cn_rule,
                    schedule=a.schedule, alpha=a.alpha, beta=a.beta, qbits=a.qbits, llr_scale=a.llr_scale,
                    layered_tile=a.layered_tile, quant_tile=a.quant_tile, stats=a.stats_json is not None,
                    max_failed=a.max_failed, channel=a.channel_spec, snr_axis=a.snr_axis, rate_match=rate_match,
-                   decoder=a.decoder, bf_weight=a.bf_weight, bf_theta=a.bf_theta)
+                   decoder=a.decoder, bf_weight=a.bf_weight, bf_theta=a.bf_theta, interleaver=interleaver,
+                   fading_block=a.fading_block)
     res = out[0]
-    info = channel_info(a.channel_spec, a.snr_axis, snrs, res.config.rate, rate_match, res.config.n, res.config.k)
+    info = channel_info(a.channel_spec, a.snr_axis, snrs, res.config.rate, rate_match, res.config.n, res.config.k,
+                        interleaver, a.fading_block)
     if rank == 0 and a.stats_json is not None:
         stats_to_json(a.stats_json, a.seed, out[2], channel=info)
     if rank == 0:
@@ -626,6 +726,8 @@ def main(argv=None):
               f"SNR axis {info['snr_axis']}  sigma " + " ".join(f"{x:.6f}" for x in info["sigma"]))
         if "rate_match" in info:
             print(rate_match_header(info["rate_match"], res.config.n, res.config.k))
+        if "interleaver" in info or "fading_block" in info:
+            print(interleave_header(info))
         for sp in res.snr_points:
             print(f"SNR {sp.snr_db:.2f} dB  FER {sp.fer:.6f}  BER {sp.ber:.6e}  "
                   f"ok {sp.successful_blocks}/{sp.total_blocks}  avg conv {sp.avg_convergence_iterations:.3f}")

@@ -29,6 +29,8 @@
 //
 // The default decoder of wimax_2304_0.5 (F = 16, Q = 4: the product crosses
 // lane groups with v_permlane16/32_swap); bit-identical to the split path.
+// Iteration 0 of the static decoder does not run this pipeline where it need
+// not: its rows and columns are independent of each other (sub_pass0_cols).
 // (An F = 8 form of this kernel for the r3/4 codes was retired in round 3:
 // tile8.hip decodes them, with E in 8-frame blocks.)
 //
@@ -354,14 +356,20 @@ __device__ __forceinline__ bool sub_p1(const SubCtx<Q> &c, int r, const SubChunk
 // the same wavefront, the one that holds the row's last edge.  Frame-less lanes
 // leave L alone.  The whole workgroup, (wavefront, lane group) pair `me` of
 // `nthr` taking every nthr-th column; the caller makes the stores visible.
+// Returns whether a table value of this lane's live frame has |t| <= 1e-10
+// (sub_p1's rare-row predicate; a NaN LLR too): the column form of iteration 0
+// (sub_pass0_cols) has no rare rows and leaves such a sub-tile to the row loop.
 template <int Q>
-__device__ __forceinline__ void sub_tanh_table(const SubCtx<Q> &c, int n, int me, int nthr) {
+__device__ __forceinline__ bool sub_tanh_table(const SubCtx<Q> &c, int n, int me, int nthr) {
+    bool tiny = false;
     for (int col = me; col < n; col += nthr) {
         const double d = *sub_c(c, col) * 0.5;
         double th[1] = {dfrom(dbits(fmin(fabs(d), 17.5)) | (dbits(d) & 0x8000000000000000ull))};
         np_tanh_n<1, LdsTanh, true>(th, c.ttab);
+        tiny |= !(fabs(th[0]) > kTiny);
         if (c.live) *sub_l(c, col) = th[0];
     }
+    return tiny && c.live;
 }
 
 // Lane-group hand-over for Q = 4 (lane = j*16 + f: group j is DPP row j) with
@@ -740,6 +748,142 @@ __device__ __forceinline__ void sub_body(SubCtx<Q> &c, int r, int m, double (&tc
     SUB_ADD(c, 6, p0, p1);
 }
 
+// Iteration 0 of the static decoder column by column, in place of its row loop
+// and A-column sweep (bit 2 of fp; LDPC_PASS0_COLS=0 keeps the row loop).  There
+// E_old = 0 and M = ch, so with T = sub_tanh_table's values in L
+//   P_r        = ((1.0 * T[c0]) * T[c1]) * ...   row r's columns ascending, the
+//                identity column last: sub_hop's multiplies (its padded 1.0s
+//                are exact no-ops),
+//   E0(r, col) = g(P_r / T[col])                 sub_p3_body's quotient, vote and atanh,
+//   S_col      = ((0.0 + E0(r0, col)) + E0(r1, col)) + ...   rows ascending.
+// Rows are independent of each other and so are columns: no chain, no flags,
+// no order waits, no LDS additions -- three phases between workgroup barriers.
+//   A  lane = (row, frame), 64 rows per step: each lane walks its row's
+//      col_idx and multiplies the gathered table values in order; P_r goes to
+//      LDS as [m][F] in the S region (unused until pass 1: the caller checks
+//      m <= k).  A frame-less lane's P is 1.0.
+//   B  lane = (column, frame), 64 columns per step, the A columns and then the
+//      identity columns: each lane walks its column's CSC list (rows
+//      ascending, DevGraph::csc_*), forms E0 from P_r (LDS) and its own T,
+//      stores it at the edge's CSR position (non-temporal; frame-less lanes at
+//      kSubOOB) and adds it to S in a register; then L = ch + S, the
+//      normalized-LLR count and the fixed-point trigger against ch (A columns
+//      only, as the sweep), the z^1 bit.  L[col] overwrites T[col] after its
+//      only reader in this phase.  div_nr and the 2q short cut are voted per
+//      wavefront step as in sub_p3_body; both are exact where they apply, so
+//      which lanes share a vote does not change a bit.  The wavefronts meet at
+//      a barrier every kP0Step list positions, so the workgroup's stores stay
+//      within a window of rows.
+// No table value is tiny here (the caller's vote), so no row is rare.  S is
+// left zero for pass 1; the caller adds my_cnt / pd into LDS as after the sweep.
+constexpr int kP0Step = 128;
+__device__ __forceinline__ int sub_group_max(int v) {  // max over the lane groups' first lanes (Q = 4)
+    return max(max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
+               max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+template <int Q>
+__device__ __forceinline__ void sub_pass0_cols(const SubCtx<Q> &c, const DevGraph &g, double *S0, uint32_t *zb,
+                                               int nllr, int me, int nthr, int &my_cnt, bool &pd) {
+    static_assert(Q == 4, "lane groups of 16");
+    constexpr int F = SubCfg<Q>::F;
+    // Edges per step of a lane: phase A's gathers in flight, phase B's index loads.  Larger steps measured
+    // the same pass 0 (profiles/r10_pass0_cols) and some of them move this kernel's spills into the row
+    // loop of the other passes.
+#ifndef LDPC_P0_UA
+#define LDPC_P0_UA 4
+#define LDPC_P0_UB 4
+#endif
+    constexpr int UA = LDPC_P0_UA, UB = LDPC_P0_UB;
+    static_assert(kP0Step % UB == 0, "a barrier window is whole steps");
+    const int m = c.m, n = g.n;
+    // A: row products
+    for (int r0 = 0; r0 < m; r0 += nthr) {
+        const int row = r0 + me, rr = min(row, m - 1);
+        const int beg = c.row_ptr[rr];
+        const int deg = row < m ? c.row_ptr[rr + 1] - beg : 0;
+        const int last = min(beg + max(deg, 1), g.nnz) - 1;  // std_form: deg >= 1
+        const int nmax = sub_group_max(deg);
+        double P = 1.0;  // 1.0 * t0 == t0 exactly
+        int cn[UA];
+#pragma unroll
+        for (int u = 0; u < UA; ++u) cn[u] = sub_col(c, min(beg + u, last));
+        for (int i = 0; i < nmax; i += UA) {
+            double t[UA];
+#pragma unroll
+            for (int u = 0; u < UA; ++u) t[u] = ld_l2((const double *)(c.Lu + sub_off(c, cn[u])));
+#pragma unroll
+            for (int u = 0; u < UA; ++u) cn[u] = sub_col(c, min(beg + i + UA + u, last));  // the next step's
+#pragma unroll
+            for (int u = 0; u < UA; ++u) P = P * ((i + u < deg && c.live) ? t[u] : 1.0);
+        }
+        if (row < m) c.S[(size_t)row * F] = P;
+    }
+    __syncthreads();  // every P_r in LDS, every gather of the table done
+    // B: columns
+    const int lastp = g.nnz - 1;
+    for (int c0 = 0; c0 < n; c0 += nthr) {
+        const int col = c0 + me, cc = min(col, n - 1);
+        const int beg = g.csc_ptr[cc];
+        const int deg = col < n ? g.csc_ptr[cc + 1] - beg : 0;
+        const int nmax = sub_group_max(deg);
+        const double chj = *sub_c(c, cc);
+        const double Tl = ld_l2(sub_l(c, cc));
+        const double T = c.live ? Tl : 1.0;  // a frame-less lane's L holds no table
+        double S = 0.0;
+        for (int i0 = 0; i0 < g.max_col_deg; i0 += kP0Step) {
+            const int iend = min(i0 + kP0Step, nmax);
+            for (int i = i0; i < iend; i += UB) {
+                int e[UB], r[UB];
+#pragma unroll
+                for (int u = 0; u < UB; ++u) {
+                    const int p = min(beg + i + u, lastp);
+                    e[u] = g.csc_edge[p];
+                    r[u] = g.csc_row[p];
+                }
+                double Pr[UB];
+#pragma unroll
+                for (int u = 0; u < UB; ++u) Pr[u] = c.S[(size_t)r[u] * F];
+#pragma unroll
+                for (int u = 0; u < UB; ++u) {
+                    const bool act = i + u < deg;
+                    const bool own = act && c.live;  // abstains from the votes and stores nothing otherwise
+                    const double P = own ? Pr[u] : 1.0;
+                    double q;
+                    if (div_nr_ok(P))
+                        q = div_nr(P, T);
+                    else
+                        q = P / T;
+                    const bool big = own && !(fabs(q) < kAtanhIdent);
+                    double E;
+                    if (__ballot(big) == 0ull) {
+                        E = 2.0 * q;
+                    } else {
+                        const AtanhCoef ac = c.coef_arg ? c.ac : coef_load();
+                        E = 2.0 * atanh_f(clip_cl(q), c.ltab, ac);
+                    }
+                    st_sub_msg(c.rE, own ? ((uint32_t)e[u] << 9) + c.lo8 : kSubOOB, E);
+                    S = act ? S + E : S;
+                }
+            }
+            __syncthreads();
+        }
+        if (col < n) {
+            const double Lj = chj + S;  // an identity column: ch + (0.0 + E)
+            if (col < c.k) {
+                if (nllr) my_cnt += (fabs(Lj) <= 7.0 && chj * Lj < 0.0) ? 1 : 0;
+                pd |= dbits(chj) != dbits(Lj);
+                if (!(Lj < 0.0)) atomicOr(zb + (col >> 5) * F + c.f, 1u << (col & 31));
+            } else if (!(Lj < 0.0)) {
+                const int q = col - c.k;
+                atomicOr(c.ib + (q >> 5) * F, 1u << (q & 31));
+            }
+            if (c.live) *sub_l(c, col) = Lj;
+        }
+    }
+    // the last barrier above: every P_r read
+    for (int i = threadIdx.x; i < m * F; i += blockDim.x) S0[i] = 0.0;
+}
+
 // Fixed-point exit (fp != 0; LDPC_FIXED_POINT=0 switches it off).  A pass is a
 // deterministic function of (E, L) and ch, its summation order fixed by the
 // p3dep waits, so a frame whose pass reproduced E and L bit for bit repeats
@@ -887,13 +1031,73 @@ __global__ __launch_bounds__(64 * kSW, 1) void tile_sub_kernel(DevGraph g, DevSt
     // passes
     int ctl = 1, vnext = 1, vgap = 1;
     const bool fpn = (fp & 2) != 0;  // the verifying passes also run the next-pass proof (LDPC_FP_NEXT)
+    // iteration 0 runs column by column (sub_pass0_cols): bit 2 of fp, P_r fits the S region, and no live
+    // frame's table value is tiny (the vote below, in the control word that pass 0 rewrites)
+    bool cols0 = (fp & 4) != 0 && m <= g.k;
+    fp &= 3;  // the exit's bits
     if (max_iter > 0) {  // iteration 0's tanh table, in L (sub_tanh_table); the other wavefronts gather it with ld_l2
         c.live = livel[f] != 0;
-        sub_tanh_table<Q>(c, g.n, me, nthr);
+        if (sub_tanh_table<Q>(c, g.n, me, nthr)) lds_st(flags + 2 * kSR + 1, 1);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         __syncthreads();
+        cols0 = cols0 && uniform(flags[2 * kSR + 1]) == 0;
     }
-    for (int it = 0; it < max_iter; ++it) {
+    int it0 = 0;
+    if (max_iter > 0 && cols0) {
+        // Iteration 0 column by column, then its syndrome and exits as in the
+        // loop below (iteration 0 never verifies: no fixed-point stop here,
+        // only the trigger for the next pass).  Ahead of the loop and not a
+        // branch of its body: there this compiler reloads ten doubles from
+        // scratch in the normal passes' P1 (profiles/r10_pass0_cols).
+        int my_cnt = 0;
+        bool pd = false;
+        sub_pass0_cols<Q>(c, g, S, zb, nllr, me, nthr, my_cnt, pd);
+        if (nllr && my_cnt) atomicAdd(cntl + f, my_cnt);
+        if (fp && pd && c.live) atomicOr((uint32_t *)pdiffl + f, 1u);
+        __syncthreads();
+        uint32_t acc = 0u;
+        for (int r = me; r < m; r += nthr) {
+            const uint32_t *ar = g.a_packed + (size_t)r * kw;
+            uint32_t par = ib[(r >> 5) * F + f] >> (r & 31);
+            for (int w = 0; w < kw; ++w) par += __builtin_popcount(ar[w] & zb[w * F + f]);
+            acc |= par & 1u;
+        }
+        if (acc) atomicOr((uint32_t *)bad + f, 1u);
+        __syncthreads();
+        if (wave == 0) {
+            bool still = false;
+            if (j == 0 && c.live) {
+                if (nllr) {
+                    const int cn = cntl[f];
+                    st.nllr_cnt[fr] = cn;
+                    if (st.nllr_hist) st.nllr_hist[(size_t)fr * st.hist_stride] = g.k > 0 ? (double)cn / g.k : 0.0;
+                }
+                const bool ok = bad[f] == 0;  // Result.OK at iteration 0, or DATA_TRANSFER_NOT_OK after the only one
+                if (ok || max_iter == 1) {
+                    st.done[fr] = 1;
+                    st.conv[fr] = ok ? 0 : -1;
+                    st.status[fr] = ok ? 0 : 1;
+                    st.iters[fr] = 1;
+                } else {
+                    still = true;
+                }
+            }
+            const unsigned long long any = __ballot(still);
+            const unsigned long long trig = __ballot(still && fp && pdiffl[f] == 0);
+            if (j == 0) {
+                livel[f] = still ? 1 : 0;
+                bad[f] = 0;
+                cntl[f] = 0;
+                pdiffl[f] = 0;
+            }
+            if (lane == 0) flags[2 * kSR + 1] = (any != 0ull ? 1 : 0) | (trig != 0ull ? 2 : 0);
+        }
+        for (int i = threadIdx.x; i < (kw + mw) * F; i += blockDim.x) zb[i] = 0u;
+        __syncthreads();
+        ctl = uniform(flags[2 * kSR + 1]);
+        it0 = (ctl & 1) ? 1 : max_iter;
+    }
+    for (int it = it0; it < max_iter; ++it) {
         c.first = it == 0;
         c.live = livel[f] != 0;
         c.ep0 = sub_epoch0(it, m);
@@ -1291,7 +1495,9 @@ hipError_t launch_tile_sub(const DevGraph &g, const DevState &st, int max_iter, 
     // LDPC_FP_NEXT=0 (bit 1 of fp): a frame stops only where no message differed, not on the next-pass proof
     const char *e = getenv("LDPC_FIXED_POINT");
     const char *en = getenv("LDPC_FP_NEXT");
-    const int fp = (!e || atoi(e) != 0) ? (1 | ((!en || atoi(en) != 0) ? 2 : 0)) : 0;
+    // LDPC_PASS0_COLS=0 (bit 2 of fp, no part of the exit): iteration 0 by the row loop, not column by column
+    const char *ec = getenv("LDPC_PASS0_COLS");
+    const int fp = ((!e || atoi(e) != 0) ? (1 | ((!en || atoi(en) != 0) ? 2 : 0)) : 0) | ((!ec || atoi(ec) != 0) ? 4 : 0);
     tile_sub_kernel<4><<<st.ntiles * 4, 64 * kSW, lds, s>>>(g, st, max_iter, nllr ? 1 : 0, g.col_idx, g.row_ptr,
                                                             kAtanhCoef, fp);
     return hipGetLastError();

@@ -674,6 +674,62 @@ int ldpc_interleaver_get(const ldpc_decoder *d, int32_t *len, int32_t *perm_out,
 int ldpc_fading_set(ldpc_decoder *d, int32_t block_len);
 int ldpc_fading_get(const ldpc_decoder *d, int32_t *block_len);
 
+/* ------------------------------------------------ HARQ (physical mode only)
+ * Retransmissions with Chase or incremental-redundancy combining in the frame
+ * source (new symbols under ABI 5: an addition only, the version stays 5).  A
+ * plan is R = n_tx transmissions, 1 <= R <= LDPC_HARQ_MAX_TX.  Transmission r
+ * sends E_r = tx_len[r] positions; position t of transmission r carries column
+ * cols_r[t]; cols is the lists one after another (sum of tx_len entries).  A
+ * column may appear in any number of transmissions, at most once within one.
+ * The order within a list is the order on the air, so a plan carries its own
+ * puncturing and interleaving.  The plan applies to ldpc_generate_frames,
+ * ldpc_phys_mc_run, _ex, _q and ldpc_bf_mc_run on that decoder; no decoder
+ * kernel knows of it.
+ * Bits: unchanged.  The info words come from seed; shortened positions (the
+ * rate-matching pattern's, which may still be set) are cleared before the
+ * parities; u_out, the counters and the statistics keep their meaning.
+ * One transmission: transmission r is exactly the interleaver contract's frame
+ * with col(t) = cols_r[t] and E = E_r, and with the Philox key
+ *   seed_r = (seed + r * 0x9E3779B97F4A7C15) mod 2^64
+ * for the noise and fade draws (transmission 0 uses the draws of a frame sent
+ * once).  Symbol s carries the positions s*bps .. s*bps + bps - 1 and takes the
+ * noise pair of counter word s; under LDPC_CH_RAYLEIGH the fade of symbol s
+ * (BPSK: of position t) is that of index s (t), or of index floor(s / block_len)
+ * under ldpc_fading_set: every transmission fades independently.  sigma is the
+ * same for every transmission.  This gives llr_r[j] in fp64 for the columns of
+ * transmission r.
+ * Combining: for every column j, llr[j] starts at +0.0; for r ascending, if
+ * transmission r carries j, llr[j] = llr[j] + llr_r[j], one fp64 addition each.
+ * A column in no transmission and not shortened is punctured: +0.0 exactly.  A
+ * shortened column is -LDPC_RM_KNOWN_LLR.  ldpc_generate_frames returns this
+ * llr; every decoder gets Lambda = -(float)llr, so the frames the decoders see
+ * are the frames ldpc_generate_frames returns.  Every output form writes every
+ * column on every launch.  A one-transmission plan whose list is tx[pi[t]]
+ * gives the frames of that pattern and interleaver: the LLRs are equal as
+ * numbers (an LLR of -0.0 becomes +0.0).
+ * ldpc_harq_set copies the lists and does no device work; n_tx == 0 (the
+ * pointers may be NULL) clears the plan.  The device tables are uploaded, and
+ * the fp64 accumulator of a chunk ([frames][n], freed with the decoder;
+ * LDPC_ENOMEM if it cannot be had) is allocated, by the first run that needs
+ * them.  LDPC_EINVAL, and the earlier plan stays in force, for: a NULL decoder;
+ * n_tx < 0 or n_tx > LDPC_HARQ_MAX_TX; a NULL pointer with n_tx > 0;
+ * tx_len[r] < 1; a column outside [0, n); a duplicate within one transmission.
+ * LDPC_EINVAL when frames are to be generated, before any device work, with a
+ * message that names the setting: a plan under the reference channel; a plan
+ * with LDPC_F_TEST_ZERO; a plan together with an interleaver; a plan together
+ * with a pattern that has punctured columns (the plan says what is sent); a
+ * plan column that the pattern shortens; E_r % bps != 0 for any r (this
+ * replaces the n % bps and E % bps checks).  The parity-mode ldpc_mc_run and
+ * ldpc_frame_order are LDPC_EINVAL while a plan is set.
+ * ldpc_harq_get: *n_tx and tx_len_out[0 .. LDPC_HARQ_MAX_TX) (zeros past n_tx;
+ * tx_len_out may be NULL); cols_out == NULL only asks for those, else cols_cap
+ * must hold the sum of the lengths (LDPC_EINVAL if too small).  A failed-frame
+ * record of ldpc_mc_stats_read still regenerates with ldpc_generate_frames on
+ * the same decoder. */
+#define LDPC_HARQ_MAX_TX 8
+int ldpc_harq_set(ldpc_decoder *d, int32_t n_tx, const int32_t *tx_len, const int32_t *cols);
+int ldpc_harq_get(const ldpc_decoder *d, int32_t *n_tx, int32_t *tx_len_out, int32_t *cols_out, int32_t cols_cap);
+
 /* ------------------------------------------------ multi-GPU (RCCL, xGMI)
  * One process per GPU; frames are sharded by global index, so the only
  * exchange is ONE all-reduce of the int64 counter matrix per Monte-Carlo step

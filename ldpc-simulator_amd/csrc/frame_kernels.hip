@@ -225,10 +225,10 @@ __global__ __launch_bounds__(256) void std_parity_kernel(DevGraph g, DevState st
 
 hipError_t launch_frames(const DevGraph &g, const DevState &st, const PhysTile &pt, uint64_t seed, int snr_point,
                          double sigma, int64_t frame0, FramesOut out, float *row_out, const FrameChannel &ch,
-                         hipStream_t s, const RateMatchDev &rm) {
-    // a rate-matching pattern, a bit interleaver (rm.E > 0) and block fading belong to the channel models (the
-    // API refuses them under the reference channel)
-    if ((rm.E > 0 || ch.fade_block != 1) && ch.model == 0) return hipErrorInvalidValue;
+                         hipStream_t s, const RateMatchDev &rm, const HarqDev &hq) {
+    // a rate-matching pattern, a bit interleaver (rm.E > 0), block fading and a HARQ plan belong to the channel
+    // models (the API refuses them under the reference channel)
+    if ((rm.E > 0 || ch.fade_block != 1 || hq.n_tx > 0) && ch.model == 0) return hipErrorInvalidValue;
     const int kw = (g.k + 31) >> 5, mw = (g.m + 31) >> 5;
     const int nblk = (kw + 3) >> 2, bpb = 16;
     const int nbc = (nblk + bpb - 1) / bpb;
@@ -251,6 +251,8 @@ hipError_t launch_frames(const DevGraph &g, const DevState &st, const PhysTile &
             std_parity_kernel<0><<<grid, 256, 0, s>>>(g, st, pt, g.a_packed);
     }
     // a channel model (physical mode only): the same bits, its own last stage
+    if (hq.n_tx > 0)
+        return launch_frame_harq(g, st, pt, seed, snr_point, sigma, frame0, out, row_out, ch, rm, hq, s);
     if (rm.E > 0)
         return launch_frame_channel_model_rm(g, st, pt, seed, snr_point, sigma, frame0, out, row_out, ch, rm, s);
     if (ch.model != 0) return launch_frame_channel_model(g, st, pt, seed, snr_point, sigma, frame0, out, row_out, ch, s);

@@ -131,6 +131,13 @@ struct ldpc_decoder {
     // the frame source's bit interleaver (ldpc_interleaver_set): transmitted position t carries column
     // tx[il_perm[t]]; empty: none.  The coherence length (ldpc_fading_set) is chan.fade_block.
     std::vector<int32_t> il_perm;
+    // the frame source's HARQ plan (ldpc_harq_set): the lengths and the column lists one after another on the
+    // host; empty: none.  The lists go to hq_dev and the fp64 accumulator of a chunk (cap x n, tile layout) is
+    // allocated on the first run that needs them, on that run's stream
+    std::vector<int32_t> hq_len, hq_cols;
+    int32_t *hq_dev = nullptr;  // LDPC_HARQ_MAX_TX x n column entries, allocated once
+    bool hq_stale = false;      // the plan changed since hq_dev was written
+    double *hq_acc = nullptr;
     // profiling (ldpc_profile_*)
     bool prof = false;
     struct Span {
@@ -306,10 +313,46 @@ DevGraph call_graph(const ldpc_decoder *d, uint32_t flags) {
     return G;
 }
 
+// The same under a HARQ plan (ldpc_harq_set): the plan says what is sent, so
+// its own lengths divide into symbols and nothing else may say what is sent.
+int harq_frames_check(const char *fn, const ldpc_decoder *d, uint32_t flags) {
+    const char *clear = "ldpc_harq_set(d, 0, NULL, NULL) clears the plan";
+    if (d->chan.model == LDPC_CH_REFERENCE)
+        return ldpc_fail(LDPC_EINVAL, "%s: a HARQ plan (ldpc_harq_set) needs a channel model, this decoder has the "
+                                      "reference channel (ldpc_channel_set; %s)", fn, clear);
+    if (flags & LDPC_F_TEST_ZERO)
+        return ldpc_fail(LDPC_EINVAL, "%s: LDPC_F_TEST_ZERO (test erasures) needs the reference channel, this decoder "
+                                      "has a HARQ plan (ldpc_harq_set; %s)", fn, clear);
+    if (!d->il_perm.empty())
+        return ldpc_fail(LDPC_EINVAL, "%s: a HARQ plan (ldpc_harq_set) carries its own order on the air, this decoder "
+                                      "also has a bit interleaver (ldpc_interleaver_set(d, 0, NULL) clears it; %s)", fn,
+                         clear);
+    if (!d->rm_punct.empty())
+        return ldpc_fail(LDPC_EINVAL, "%s: a HARQ plan (ldpc_harq_set) says what is sent, this decoder's rate-matching "
+                                      "pattern (ldpc_rate_match_set) also punctures %d columns (%s)", fn,
+                         (int)d->rm_punct.size(), clear);
+    if (!d->rm_short.empty())
+        for (int32_t c : d->hq_cols)
+            if (std::binary_search(d->rm_short.begin(), d->rm_short.end(), c))
+                return ldpc_fail(LDPC_EINVAL, "%s: the HARQ plan (ldpc_harq_set) sends column %d, which the rate-matching "
+                                              "pattern (ldpc_rate_match_set) shortens (%s)", fn, c, clear);
+    if (d->chan.fade_block > 1 && d->chan.model != LDPC_CH_RAYLEIGH)
+        return ldpc_fail(LDPC_EINVAL, "%s: block fading (ldpc_fading_set, block_len = %d) needs LDPC_CH_RAYLEIGH, this "
+                                      "decoder's channel model is %d (ldpc_fading_set(d, 1) clears it)", fn,
+                         d->chan.fade_block, d->chan.model);
+    for (size_t r = 0; r < d->hq_len.size(); ++r)
+        if (d->hq_len[r] % d->chan.bps != 0)
+            return ldpc_fail(LDPC_EINVAL, "%s: transmission %d of the HARQ plan (ldpc_harq_set) sends E_r = %d positions, "
+                                          "not a multiple of bps = %d (the channel's bits per symbol)", fn, (int)r,
+                             d->hq_len[r], d->chan.bps);
+    return LDPC_OK;
+}
+
 // What a call that generates frames under the decoder's channel model must
 // hold (no device work): the code length divides into symbols, and the
 // test-only erasures belong to the reference channel.
 int channel_frames_check(const char *fn, const ldpc_decoder *d, uint32_t flags) {
+    if (!d->hq_len.empty()) return harq_frames_check(fn, d, flags);
     const int n_fill = (int)(d->rm_punct.size() + d->rm_short.size());
     if (n_fill > 0 && d->chan.model == LDPC_CH_REFERENCE)
         return ldpc_fail(LDPC_EINVAL, "%s: a rate-matching pattern (ldpc_rate_match_set) needs a channel model, this "
@@ -343,6 +386,9 @@ int channel_frames_check(const char *fn, const ldpc_decoder *d, uint32_t flags) 
 
 // The parity-mode entries reproduce the reference: its channel only.
 int channel_parity_check(const char *fn, const ldpc_decoder *d) {
+    if (!d->hq_len.empty())
+        return ldpc_fail(LDPC_EINVAL, "%s: parity mode sends every code once; a HARQ plan is physical mode's "
+                                      "(ldpc_harq_set(d, 0, NULL, NULL) clears the plan)", fn);
     if (!d->rm_punct.empty() || !d->rm_short.empty())
         return ldpc_fail(LDPC_EINVAL, "%s: parity mode sends every code whole; rate matching is physical mode's "
                                       "(ldpc_rate_match_set(d, 0, NULL, 0, NULL) clears the pattern)", fn);
@@ -390,6 +436,40 @@ int rate_match_dev(ldpc_decoder *d, hipStream_t s, ldpc::RateMatchDev *out) {
     out->E = t.E;
     out->n_fill = t.n_fill;
     out->n_short = (int)d->rm_short.size();
+    return LDPC_OK;
+}
+
+// The decoder's HARQ plan for the frame source's kernels: nothing (n_tx = 0)
+// without one, else its column lists in device memory, uploaded on stream s if
+// the plan changed since they were (a copy from pageable host memory, as
+// rate_match_dev's), and the chunk's fp64 accumulator.
+int harq_dev(ldpc_decoder *d, hipStream_t s, ldpc::HarqDev *out) {
+    *out = ldpc::HarqDev{};
+    if (d->hq_len.empty()) return LDPC_OK;
+    const DevGraph &G = d->g->dg;
+    if (d->hq_len.size() > (size_t)ldpc::kHarqMaxTx || d->hq_cols.size() > (size_t)ldpc::kHarqMaxTx * (size_t)G.n)
+        return ldpc_fail(LDPC_EINVAL, "the HARQ plan does not fit the code: %d transmissions, %zu positions",
+                         (int)d->hq_len.size(), d->hq_cols.size());
+    if (!d->hq_dev) {
+        if (int rc = dev_alloc(&d->hq_dev, (size_t)ldpc::kHarqMaxTx * (size_t)G.n)) return rc;
+        d->hq_stale = true;
+    }
+    if (!d->hq_acc)
+        if (int rc = dev_alloc(&d->hq_acc, (size_t)d->cap_tiles * kTile * (size_t)G.n)) return rc;
+    if (d->hq_stale) {
+        HIP_TRY(hipMemcpyAsync(d->hq_dev, d->hq_cols.data(), sizeof(int32_t) * d->hq_cols.size(),
+                               hipMemcpyHostToDevice, s));
+        d->hq_stale = false;
+    }
+    out->cols = d->hq_dev;
+    out->acc = d->hq_acc;
+    out->n_tx = (int)d->hq_len.size();
+    int off = 0;
+    for (int r = 0; r < out->n_tx; ++r) {
+        out->tx_len[r] = d->hq_len[(size_t)r];
+        out->tx_off[r] = off;
+        off += d->hq_len[(size_t)r];
+    }
     return LDPC_OK;
 }
 
@@ -907,6 +987,8 @@ int ldpc_decoder_destroy(ldpc_decoder *d) {
     (void)hipFree(d->ms_slots);
     (void)hipFree(d->ms_tile);
     (void)hipFree(d->rm_dev);
+    (void)hipFree(d->hq_dev);
+    (void)hipFree(d->hq_acc);
     for (auto &sp : d->spans) {
         (void)hipEventDestroy(sp.a);
         (void)hipEventDestroy(sp.b);
@@ -1079,12 +1161,13 @@ int ldpc_generate_frames(ldpc_decoder *d, uint64_t seed, int32_t snr_point, doub
         l_dev = llr_out;
     }
     ldpc::RateMatchDev rm;
-    if ((rc = ensure_pbits(d, G)) || (rc = rate_match_dev(d, s, &rm))) {
+    ldpc::HarqDev hq;
+    if ((rc = ensure_pbits(d, G)) || (rc = rate_match_dev(d, s, &rm)) || (rc = harq_dev(d, s, &hq))) {
         (void)hipFree(dev_ptrs ? nullptr : u_dev);
         return rc;
     }
     HIP_TRY(ldpc::launch_frames(G, d->st, phys_tile(d), seed, snr_point, sigma, frame0, ldpc::kFramesCh, nullptr,
-                                d->chan, s, rm));
+                                d->chan, s, rm, hq));
     // export writes u only for j<k, at [f][k]: give it the [count][k] buffer
     HIP_TRY(ldpc::launch_export_frames(G, d->st, u_dev, l_dev, s));
     if (!dev_ptrs) {
@@ -1817,6 +1900,8 @@ int phys_mc_any(const char *fn, ldpc_decoder *d, const ldpc_graph *gp, uint64_t 
     if (int rc = ensure_pbits(d, G)) return rc;
     ldpc::RateMatchDev rm;
     if (int rc = rate_match_dev(d, s, &rm)) return rc;
+    ldpc::HarqDev hq;
+    if (int rc = harq_dev(d, s, &hq)) return rc;
     const int need = n_points * LDPC_MC_NCOUNT;
     if (d->counters_cap < need) {
         (void)hipFree(d->counters);
@@ -1842,7 +1927,7 @@ int phys_mc_any(const char *fn, ldpc_decoder *d, const ldpc_graph *gp, uint64_t 
             HIP_TRY(timed(d, LDPC_K_GEN, s, [&] {
                 return ldpc::launch_frames(G, st, phys_tile(d), seed, p, sigmas[p], frame0 + start,
                                            lds ? ldpc::kFramesRowLambda : ldpc::kFramesTileLambda, rows, d->chan, s,
-                                           rm);
+                                           rm, hq);
             }));
             if (lds) {
                 HIP_TRY(timed(d, LDPC_K_PHYS, s, [&] {
@@ -2258,6 +2343,8 @@ int ldpc_phys_mc_run_q(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int
     if (int rc = ensure_pbits(d, G)) return rc;
     ldpc::RateMatchDev rm;
     if (int rc = rate_match_dev(d, s, &rm)) return rc;
+    ldpc::HarqDev hq;
+    if (int rc = harq_dev(d, s, &hq)) return rc;
     const int need = n_points * LDPC_MC_NCOUNT;
     if (d->counters_cap < need) {
         (void)hipFree(d->counters);
@@ -2282,7 +2369,7 @@ int ldpc_phys_mc_run_q(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int
             HIP_TRY(timed(d, LDPC_K_GEN, s, [&] {
                 return ldpc::launch_frames(G, st, phys_tile(d), seed, p, sigmas[p], frame0 + start,
                                            rule.tile ? ldpc::kFramesTileLambda : ldpc::kFramesRowLambda, rows,
-                                           d->chan, s, rm);
+                                           d->chan, s, rm, hq);
             }));
             if (rule.tile) {
                 if (ms.hist) HIP_TRY(ldpc::launch_mc_stats_slots(ms.slot_frame, ms.frame_base, cnt, s));
@@ -2456,6 +2543,8 @@ int ldpc_bf_mc_run(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int32_t
     if (int rc = ensure_pbits(d, G)) return rc;
     ldpc::RateMatchDev rm;
     if (int rc = rate_match_dev(d, s, &rm)) return rc;
+    ldpc::HarqDev hq;
+    if (int rc = harq_dev(d, s, &hq)) return rc;
     const int need = n_points * LDPC_MC_NCOUNT;
     if (d->counters_cap < need) {
         (void)hipFree(d->counters);
@@ -2478,7 +2567,7 @@ int ldpc_bf_mc_run(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int32_t
             float *rows = (float *)d->llr_stage;  // the frames as fp32 Lambda rows, as ldpc_phys_mc_run's LDS path
             HIP_TRY(timed(d, LDPC_K_GEN, s, [&] {
                 return ldpc::launch_frames(G, st, phys_tile(d), seed, p, sigmas[p], frame0 + start,
-                                           ldpc::kFramesRowLambda, rows, d->chan, s, rm);
+                                           ldpc::kFramesRowLambda, rows, d->chan, s, rm, hq);
             }));
             HIP_TRY(timed(d, LDPC_K_PHYS, s, [&] {
                 return bf_launch(P, k, nullptr, rows, 2, cnt, max_iter, nullptr, nullptr, nullptr, nullptr, nullptr,
@@ -2603,6 +2692,41 @@ int ldpc_fading_get(const ldpc_decoder *d, int32_t *block_len) {
     if (!d) return ldpc_fail(LDPC_EINVAL, "ldpc_fading_get: NULL decoder");
     if (!block_len) return ldpc_fail(LDPC_EINVAL, "ldpc_fading_get: NULL block_len");
     *block_len = d->chan.fade_block;
+    return LDPC_OK;
+}
+
+// ------------------------------------------------------------------ HARQ
+int ldpc_harq_set(ldpc_decoder *d, int32_t n_tx, const int32_t *tx_len, const int32_t *cols) {
+    const char *fn = "ldpc_harq_set";
+    if (!d) return ldpc_fail(LDPC_EINVAL, "%s: NULL decoder", fn);
+    const std::string err = ldpc::harq_validate(d->g->dg.n, n_tx, tx_len, cols);
+    if (!err.empty()) return ldpc_fail(LDPC_EINVAL, "%s: %s", fn, err.c_str());
+    size_t total = 0;
+    for (int32_t r = 0; r < n_tx; ++r) total += (size_t)tx_len[r];
+    if (n_tx > 0) {
+        d->hq_len.assign(tx_len, tx_len + n_tx);
+        d->hq_cols.assign(cols, cols + total);
+    } else {
+        d->hq_len.clear();
+        d->hq_cols.clear();
+    }
+    d->hq_stale = true;
+    return LDPC_OK;
+}
+
+int ldpc_harq_get(const ldpc_decoder *d, int32_t *n_tx, int32_t *tx_len_out, int32_t *cols_out, int32_t cols_cap) {
+    const char *fn = "ldpc_harq_get";
+    if (!d) return ldpc_fail(LDPC_EINVAL, "%s: NULL decoder", fn);
+    if (!n_tx || cols_cap < 0 || (cols_cap > 0 && !cols_out)) return ldpc_fail(LDPC_EINVAL, "%s: bad arguments", fn);
+    *n_tx = (int32_t)d->hq_len.size();
+    if (tx_len_out)
+        for (int r = 0; r < LDPC_HARQ_MAX_TX; ++r) tx_len_out[r] = r < *n_tx ? d->hq_len[(size_t)r] : 0;
+    if (cols_out) {
+        if ((size_t)cols_cap < d->hq_cols.size())
+            return ldpc_fail(LDPC_EINVAL, "%s: capacity %d is too small for a plan of %zu positions", fn, cols_cap,
+                             d->hq_cols.size());
+        std::copy(d->hq_cols.begin(), d->hq_cols.end(), cols_out);
+    }
     return LDPC_OK;
 }
 

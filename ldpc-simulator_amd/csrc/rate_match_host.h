@@ -124,6 +124,39 @@ inline bool interleaver_apply(RateMatchTables &t, const std::vector<int32_t> &pe
     return true;
 }
 
+// ------------------------------------------------------------------- HARQ
+// (include/ldpc_hip.h "HARQ")  Empty when {tx_len, cols} is a plan of n_tx
+// transmissions a code with n columns can carry (n_tx == 0: none), else what is
+// wrong with it (the contract's list, in its order).  cols is read only as far
+// as the lengths checked so far say.
+constexpr int kHarqMaxTxHost = 8;  // LDPC_HARQ_MAX_TX
+inline std::string harq_validate(int n, int32_t n_tx, const int32_t *tx_len, const int32_t *cols) {
+    if (n_tx < 0 || n_tx > kHarqMaxTxHost)
+        return "n_tx = " + std::to_string(n_tx) + " is outside [0, " + std::to_string(kHarqMaxTxHost) +
+               "] (LDPC_HARQ_MAX_TX)";
+    if (n_tx > 0 && (!tx_len || !cols)) return "NULL tx_len or cols with n_tx > 0";
+    for (int32_t r = 0; r < n_tx; ++r)
+        if (tx_len[r] < 1 || tx_len[r] > n)
+            return "tx_len[" + std::to_string(r) + "] = " + std::to_string(tx_len[r]) +
+                   (tx_len[r] < 1 ? " < 1" : " > n = " + std::to_string(n) + " (a duplicate column within the transmission)");
+    std::vector<int32_t> seen((size_t)std::max(n, 0), -1);  // the last transmission that carried the column
+    size_t off = 0;
+    for (int32_t r = 0; r < n_tx; ++r) {
+        for (int32_t t = 0; t < tx_len[r]; ++t) {
+            const int32_t c = cols[off + (size_t)t];
+            if (c < 0 || c >= n)
+                return "column " + std::to_string(c) + " (transmission " + std::to_string(r) + ", position " +
+                       std::to_string(t) + ") is outside [0, " + std::to_string(n) + ")";
+            if (seen[(size_t)c] == r)
+                return "column " + std::to_string(c) + " is listed twice in transmission " + std::to_string(r) +
+                       " (duplicate)";
+            seen[(size_t)c] = r;
+        }
+        off += (size_t)tx_len[r];
+    }
+    return std::string();
+}
+
 // The last gate before an upload: every index a kernel gathers or scatters with
 // lies in [0, n), tx_col and fill_col together name every column exactly once,
 // and the block fits the device allocation.

@@ -327,9 +327,27 @@ struct RateMatchDev {
     const uint32_t *umask = nullptr;    // [kw] AND mask of st.ubits (shortened bits clear)
     int E = 0, n_fill = 0, n_short = 0;
 };
+// A decoder's HARQ plan as the frame source's kernels read it (include/ldpc_hip.h
+// "HARQ"; frame_harq.hip).  The default (n_tx == 0) is no plan: launch_frames
+// runs as it does without one.  With a plan, rm carries at most shortened
+// columns (rm.umask, rm.n_short): the plan says what is sent.
+constexpr int kHarqMaxTx = 8;  // LDPC_HARQ_MAX_TX
+struct HarqDev {
+    const int32_t *cols = nullptr;  // the transmissions' column lists, one after another
+    double *acc = nullptr;          // fp64 accumulator of the chunk, tile layout [tile][n][64] as DevState::ch
+    int n_tx = 0;
+    int tx_len[kHarqMaxTx] = {};    // E_r
+    int tx_off[kHarqMaxTx] = {};    // where transmission r's list starts in cols
+};
 hipError_t launch_frames(const DevGraph &g, const DevState &st, const PhysTile &pt, uint64_t seed, int snr_point,
                          double sigma, int64_t frame0, FramesOut out, float *row_out, const FrameChannel &ch,
-                         hipStream_t s, const RateMatchDev &rm = RateMatchDev{});
+                         hipStream_t s, const RateMatchDev &rm = RateMatchDev{}, const HarqDev &hq = HarqDev{});
+// The last stage of launch_frames under a HARQ plan (frame_harq.hip; hq.n_tx > 0,
+// ch.model != 0, every hq.tx_len[r] % ch.bps == 0): zero the accumulator, add
+// transmission 0 .. n_tx - 1 into it, write the requested form from it.
+hipError_t launch_frame_harq(const DevGraph &g, const DevState &st, const PhysTile &pt, uint64_t seed, int snr_point,
+                             double sigma, int64_t frame0, FramesOut out, float *row_out, const FrameChannel &ch,
+                             const RateMatchDev &rm, const HarqDev &hq, hipStream_t s);
 // The last stage of launch_frames under a channel model (frame_channel_models.hip;
 // ch.model != 0, g.n % ch.bps == 0): the codeword bits are in st.ubits / pt.pbits /
 // pt.wpar already.

@@ -455,6 +455,38 @@ class Decoder:
         check("ldpc_fading_get", _lib.lib().ldpc_fading_get(self._h, ctypes.byref(n)))
         return int(n.value)
 
+    def set_harq(self, plan):
+        """The frame source's HARQ plan for generate(), phys_mc_run() and
+        bitflip_mc_run() on this decoder from now on (ldpc_harq_set): a
+        harq.HarqPlan; None clears it.  Every transmission's LLRs are added
+        per column before the decoders see the frame.  No device work."""
+        from .harq import HarqPlan
+        if plan is None:
+            check("ldpc_harq_set", _lib.lib().ldpc_harq_set(self._h, 0, None, None))
+            return
+        if not isinstance(plan, HarqPlan):
+            raise ValueError(f"set_harq takes a HarqPlan or None, got {type(plan).__name__}")
+        plan.validate(self.graph.n)
+        lens = _lib.as_i32(plan.lengths)
+        cols = _lib.as_i32([c for t in plan.tx for c in t])
+        check("ldpc_harq_set", _lib.lib().ldpc_harq_set(self._h, len(lens), _lib.i32p(lens), _lib.i32p(cols)))
+
+    @property
+    def harq(self):
+        """The plan in force as a harq.HarqPlan (kind "custom": the library
+        keeps the lists only), None without one."""
+        from .harq import MAX_TX, HarqPlan
+        n = _lib.c_i32()
+        lens = np.zeros(MAX_TX, np.int32)
+        check("ldpc_harq_get", _lib.lib().ldpc_harq_get(self._h, ctypes.byref(n), _lib.i32p(lens), None, 0))
+        if n.value == 0:
+            return None
+        cols = np.zeros(int(lens.sum()), np.int32)
+        check("ldpc_harq_get", _lib.lib().ldpc_harq_get(self._h, ctypes.byref(n), _lib.i32p(lens), _lib.i32p(cols),
+                                                        len(cols)))
+        offs = np.concatenate([[0], np.cumsum(lens[:n.value])])
+        return HarqPlan(tuple(tuple(int(x) for x in cols[offs[r]:offs[r + 1]]) for r in range(n.value)))
+
     def generate(self, seed, snr_point, sigma, frame0, count, test_zero=False):
         """On-device synthetic frames (u bits, channel LLRs) copied back for testing.
         test_zero: the frame source's test-only erasures (LDPC_F_TEST_ZERO)."""

@@ -520,6 +520,175 @@ def _simulate_graph(H, name, t0, snrs, blocks, max_iter, seed, chunk, device, ra
     return (res, ctr, st) if stats else (res, ctr)
 
 
+def check_harq_args(harq, channel, mode, interleaver=None, rate_match=None):
+    """ValueError for a HARQ plan simulate_harq() cannot honour (before any
+    code is loaded): it needs mode="physical" and a channel model, and neither
+    an interleaver nor punctured columns (the plan says what is sent, in which
+    order).  A spec string is checked for its form here and resolved once the
+    code is known (harq.resolve)."""
+    from .harq import HarqPlan, split_spec
+    if isinstance(harq, str):
+        split_spec(harq)
+    elif not isinstance(harq, HarqPlan):
+        raise ValueError(f"harq must be a HarqPlan or a spec string, got {type(harq).__name__}")
+    if mode != "physical":
+        raise ValueError("a HARQ plan needs mode='physical' (parity mode sends every code once)")
+    if channel is None or channel.is_reference:
+        raise ValueError("a HARQ plan needs a channel model (channel=ChannelSpec('awgn' / 'rayleigh', ...)): the "
+                         "reference channel sends every code once")
+    if interleaver is not None and not (isinstance(interleaver, str) and interleaver.strip().lower() == "none"):
+        raise ValueError("a HARQ plan carries its own order on the air: it takes no interleaver")
+    if rate_match is not None and rate_match.punctured:
+        raise ValueError("a HARQ plan says what is sent: it takes no puncturing pattern (shortening may stay)")
+    return harq
+
+
+def harq_point(counters, lengths, k_info, bps):
+    """The HARQ figures of one SNR point from the counters of the R sweeps,
+    counters[r] being the run with the first r + 1 transmissions (int64 [R, 7]
+    in NCOUNT's order) and lengths[r] = E_r:
+      fer_after[r]      failed / frames of run r
+      ber_after[r]      err_bits / (k_info frames)
+      avg_iterations[r] iterations / frames
+      p_tx[r]           the probability that transmission r is sent: 1 for
+                        r = 0, fer_after[r - 1] after
+      avg_tx            sum p_tx
+      bits_sent         sum p_tx[r] E_r
+      throughput        k_info (1 - fer_after[R - 1]) / (bits_sent / bps),
+                        information bits per symbol
+    p_tx treats the failures as nested: it is exact where a frame that decodes
+    from r transmissions also decodes from more, which combining makes very
+    nearly but not strictly so."""
+    c = np.asarray(counters, dtype=np.int64).reshape(-1, NCOUNT)
+    R = c.shape[0]
+    if len(lengths) != R:
+        raise ValueError(f"{len(lengths)} transmission lengths for {R} runs")
+    frames = c[:, 0].astype(np.float64)
+    ok = frames > 0
+    safe = np.where(ok, frames, 1.0)
+    fer = np.where(ok, c[:, 1] / safe, 0.0)
+    ber = np.where(ok, c[:, 2] / (float(k_info) * safe), 0.0) if k_info else np.zeros(R)
+    avg_it = np.where(ok, c[:, 6] / safe, 0.0)
+    p_tx = np.concatenate([[1.0], fer[:-1]])
+    bits = float(np.sum(p_tx * np.asarray(lengths, dtype=np.float64)))
+    return {"fer_after": [float(x) for x in fer], "ber_after": [float(x) for x in ber],
+            "avg_iterations": [float(x) for x in avg_it], "p_tx": [float(x) for x in p_tx],
+            "avg_tx": float(p_tx.sum()), "bits_sent": bits,
+            "throughput": float(k_info) * (1.0 - float(fer[-1])) / (bits / float(bps))}
+
+
+def simulate_harq(matrix, snrs, blocks, max_iter, harq, seed=20260213, chunk=65536, device=0, rank=0, world=1,
+                  allreduce=None, mode="physical", cn_rule="spa", schedule="flooding", alpha=0.75, beta=0.5,
+                  qbits=None, llr_scale=4.0, layered_tile=False, quant_tile=False, stats=False, max_failed=0,
+                  channel=None, snr_axis=None, rate_match=None, decoder="sumproduct", bf_weight=0.0, bf_theta=0.0,
+                  interleaver=None, fading_block=1):
+    """A physical-mode sweep under a HARQ plan (harq: a harq.HarqPlan, or one of
+    its spec strings chase:R[:E], ir:R:E, file:PATH, resolved against the code
+    and the pattern's shortened columns).  The keywords are simulate()'s
+    physical-mode ones.  The sweep runs R times on the same seed, run r with the
+    plan's first r + 1 transmissions (HarqPlan.truncated), so run r decodes
+    exactly the frames a receiver holds after transmission r, each regenerable
+    from (seed, point, frame index).  Returns a dict:
+      "plan"      HarqPlan.info()
+      "sigma"     sigma per point (the same for every transmission)
+      "counters"  int64 [R, points, 7]
+      "points"    per SNR point snr_db, frames and harq_point()'s figures:
+                  fer_after, ber_after, avg_iterations, p_tx, avg_tx, bits_sent,
+                  throughput
+      "stats"     stats=True: per run the per-point statistics of simulate()
+    p_tx treats the failures as nested (harq_point), which is exact where a
+    frame that decodes from r transmissions also decodes from more.  An Eb/N0
+    axis uses the first transmission's rate (k - n_short) / E_0.
+    ValueError before any device call for a plan without a channel model, with
+    an interleaver, with a puncturing pattern, or in parity mode."""
+    bf_weight, bf_theta = check_decoder_args(decoder, bf_weight, bf_theta, mode, cn_rule, schedule, qbits,
+                                             layered_tile, quant_tile, False)
+    bf = (bf_weight, bf_theta) if decoder == "bitflipping" else None
+    check_harq_args(harq, channel, mode, interleaver, rate_match)
+    snr_axis = check_channel_args(channel, snr_axis, mode)
+    rate_match = check_rate_match_args(rate_match, channel, mode)
+    _, fading_block = check_interleave_args(None, fading_block, channel, mode)
+    from .channel import sigmas_for_axis
+    from .code import EncoderDecoderData, load_committed_code
+    from .device import Decoder, Graph, phys_flags, phys_quant_args, phys_rule_args
+    from .harq import resolve as resolve_harq
+    check_stats_args(stats, max_failed, mode, world)
+    phys_rule_args(cn_rule, schedule, alpha, beta)
+    if qbits is not None:
+        phys_quant_args(cn_rule, alpha, beta, qbits, llr_scale)
+    elif quant_tile:
+        raise ValueError("quant_tile needs qbits (the fixed-point decoder)")
+    phys_flags(tile=layered_tile, schedule=schedule, qtile=quant_tile)
+    if isinstance(matrix, str) and matrix in IRA_CODES:
+        from . import ira
+        H = getattr(ira, IRA_CODES[matrix])()
+        m, n = H.shape
+        k = n - m
+        h_src = h_phys = H
+    else:
+        if isinstance(matrix, EncoderDecoderData):
+            edd = matrix
+        elif isinstance(matrix, str) and os.path.exists(matrix):
+            edd = EncoderDecoderData(matrix)
+        else:
+            edd = load_committed_code(matrix)
+        n, k = edd._n, edd._k
+        h_src, h_phys = edd._h_std, None
+    shortened = rate_match.shortened if rate_match is not None else ()
+    if rate_match is not None:
+        rate_match.validate(n, k)
+    plan = resolve_harq(harq, n, shortened).validate(n, shortened, channel.bps)
+    k_info = k - len(shortened)
+    sigmas = sigmas_for_axis(channel, snr_axis, snrs, k_info / plan.n_sent(0))
+    g = Graph(h_src, device=device)
+    gp = g if h_phys is h_src else Graph(edd.physical_matrix(), device=device)
+    dec = Decoder(g, Decoder.fit_slots(g, min(max(1, shard(int(blocks), rank, world)[1]), chunk)))
+    dec.set_channel(channel)
+    dec.set_rate_match(rate_match)
+    dec.set_fading_block(fading_block)
+    if stats:
+        dec.mc_stats(True, max_failed)
+
+    def counter_fn(sigmas, cnt, frame0):
+        if bf is not None:
+            return dec.bitflip_mc_run(gp, seed, sigmas, cnt, frame0, max_iter, weight=bf[0], theta=bf[1])
+        return dec.phys_mc_run(gp, seed, sigmas, cnt, frame0, max_iter, cn=cn_rule, schedule=schedule, alpha=alpha,
+                               beta=beta, qbits=qbits, llr_scale=llr_scale, tile=layered_tile, qtile=quant_tile)
+    ctrs, sts = [], []
+    for r in range(1, plan.R + 1):
+        dec.set_harq(plan.truncated(r))
+        out = run_sweep(dec, snrs, blocks, max_iter, seed=seed, rank=rank, world=world, allreduce=allreduce,
+                        counter_fn=counter_fn, stats_fn=(lambda p: dec.mc_stats_read(p, max_iter)) if stats else None,
+                        sigmas=sigmas)
+        ctr, st = out if stats else (out, None)
+        ctrs.append(np.asarray(ctr, dtype=np.int64))
+        sts.append(st)
+    ctrs = np.stack(ctrs)
+    pts = []
+    for p, snr in enumerate(snrs):
+        pts.append({"snr_db": float(snr), "frames": int(ctrs[0, p, 0]),
+                    **harq_point(ctrs[:, p], plan.lengths, k_info, channel.bps)})
+    res = {"plan": plan.info(), "sigma": [float(x) for x in sigmas], "counters": ctrs, "points": pts}
+    if stats:
+        res["stats"] = sts
+    return res
+
+
+def harq_header(info):
+    """The command line's header line of a HARQ sweep."""
+    step = f"  step {info['step']}" if "step" in info else ""
+    return f"HARQ {info['kind']}  R {info['R']}  E_r " + " ".join(str(e) for e in info["E"]) + step
+
+
+def harq_to_json(path, seed, res):
+    """Write simulate_harq()'s result (without the statistics) with its seed."""
+    import json
+    doc = {"seed": int(seed), "plan": res["plan"], "sigma": res["sigma"], "points": res["points"],
+           "counters": np.asarray(res["counters"]).tolist()}
+    with open(path, "w") as f:
+        json.dump(doc, f, indent=1)
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description="GPU BER/FER sweep (main.py semantics, AWGN mode 1, BPSK)")
     ap.add_argument("--matrix", required=True,
@@ -583,6 +752,13 @@ def build_parser():
     ap.add_argument("--fading-block", default=None, metavar="L|frame",
                     help="with --channel rayleigh: symbols (BPSK: bits) that share a fade (default 1); frame: one "
                          "fade per frame")
+    ap.add_argument("--harq", default=None, metavar="SPEC",
+                    help="with --channel awgn / rayleigh: retransmissions with combining in the frame source: "
+                         "chase:R[:E] (the same E columns R times), ir:R:E (consecutive windows of E columns of the "
+                         "circular buffer) or file:PATH (a transmission's columns per line); the sweep runs once per "
+                         "transmission and reports FER after each, the average transmissions and the throughput")
+    ap.add_argument("--harq-json", default=None, metavar="PATH",
+                    help="with --harq: write the plan, the per-point HARQ figures and the counters to PATH")
     return ap
 
 
@@ -636,6 +812,18 @@ def parse_args(argv=None):
         except ValueError:
             ap.error(f"--fading-block takes an integer >= 1 or 'frame', got {a.fading_block!r}")
     a.fading_block = 1 if a.fading_block is None else a.fading_block
+    if a.harq_json is not None and a.harq is None:
+        ap.error("--harq-json needs --harq")
+    if a.harq is not None:
+        if a.mode != "physical" or a.channel == "reference":
+            ap.error("--harq needs --mode physical --channel awgn or rayleigh")
+        if a.interleaver is not None and a.interleaver.strip().lower() != "none":
+            ap.error("--harq carries its own order on the air: it takes no --interleaver")
+        if a.puncture is not None:
+            ap.error("--harq says what is sent: it takes no --puncture (--shorten may stay)")
+        if a.normalized_llr or a.output_json or a.output_csv or a.stats_json is not None:
+            ap.error("--harq writes --harq-json: --normalized-llr, --output-json, --output-csv and --stats-json do "
+                     "not apply to it")
     a.llr_scale = 4.0 if a.llr_scale is None else a.llr_scale
     a.alpha = 0.75 if a.alpha is None else a.alpha
     a.beta = 0.5 if a.beta is None else a.beta
@@ -644,6 +832,8 @@ def parse_args(argv=None):
         a.snr_axis = check_channel_args(a.channel_spec, a.snr_axis, a.mode)
         a.interleaver, a.fading_block = check_interleave_args(a.interleaver, a.fading_block, a.channel_spec, a.mode)
         check_ira_mode(a.matrix, a.mode)
+        if a.harq is not None:
+            check_harq_args(a.harq, a.channel_spec, a.mode)
         check_decoder_args(a.decoder, a.bf_weight, a.bf_theta, a.mode)
         phys_flags(tile=a.layered_tile, schedule=a.schedule)
         phys_rule_args(a.cn_rule, a.schedule, a.alpha, a.beta)
@@ -685,6 +875,33 @@ def rate_match_header(rm_info, n, k):
             f"effective rate {rm_info['rate']:.6f}")
 
 
+def main_harq(a, snrs, rate_match, rank, world, local, allreduce, comm):
+    """main() under --harq: simulate_harq and its own report."""
+    from .harq import resolve as resolve_harq
+    try:  # resolved here, without a device, so that a bad plan ends before any device call
+        n, k = code_shape(a.matrix)
+        shortened = rate_match.shortened if rate_match is not None else ()
+        plan = resolve_harq(a.harq, n, shortened).validate(n, shortened, a.channel_spec.bps)
+    except (ValueError, OSError) as e:
+        raise SystemExit(f"--harq: {e}")
+    res = simulate_harq(a.matrix, snrs, a.blocks, a.iterations, plan, seed=a.seed, device=local, rank=rank,
+                        world=world, allreduce=allreduce, mode=a.mode, cn_rule=a.cn_rule, schedule=a.schedule,
+                        alpha=a.alpha, beta=a.beta, qbits=a.qbits, llr_scale=a.llr_scale, layered_tile=a.layered_tile,
+                        quant_tile=a.quant_tile, channel=a.channel_spec, snr_axis=a.snr_axis, rate_match=rate_match,
+                        decoder=a.decoder, bf_weight=a.bf_weight, bf_theta=a.bf_theta, fading_block=a.fading_block)
+    if rank == 0:
+        print(f"channel {a.channel_spec.model}  modulation {a.channel_spec.modulation}  demap {a.channel_spec.demap}  "
+              f"SNR axis {a.snr_axis}  sigma " + " ".join(f"{x:.6f}" for x in res["sigma"]))
+        print(harq_header(res["plan"]))
+        for pt in res["points"]:
+            print(f"SNR {pt['snr_db']:.2f} dB  FER after r " + " ".join(f"{x:.6f}" for x in pt["fer_after"])
+                  + f"  avg tx {pt['avg_tx']:.4f}  throughput {pt['throughput']:.4f} bit/symbol")
+        if a.harq_json:
+            harq_to_json(a.harq_json, a.seed, res)
+    if comm is not None:
+        comm.close()
+
+
 def main(argv=None):
     a = parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -702,6 +919,8 @@ def main(argv=None):
         rate_match = cli_rate_match(a)  # the code's n and k without a device
     except ValueError as e:
         raise SystemExit(f"--puncture / --shorten: {e}")
+    if a.harq is not None:
+        return main_harq(a, snrs, rate_match, rank, world, local, allreduce, comm)
     interleaver = a.interleaver
     if interleaver is not None:
         try:  # resolved here, without a device, so that the header and the JSON name what ran

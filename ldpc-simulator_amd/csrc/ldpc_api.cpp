@@ -13,6 +13,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -252,6 +253,30 @@ int ensure_pbits(ldpc_decoder *d, const DevGraph &P) {
     if (d->pbits) return LDPC_OK;
     const size_t mw = (size_t)(P.m + 31) / 32, mw32 = (mw + 31) / 32;
     return dev_alloc(&d->pbits, (size_t)d->cap_tiles * (mw + mw32) * kTile);  // pbits + wpar
+}
+
+// A Monte-Carlo run's counters, LDPC_MC_NCOUNT per point: on the device, zeroed on stream s.
+int counters_begin(ldpc_decoder *d, int n_points, hipStream_t s) {
+    const int need = n_points * LDPC_MC_NCOUNT;
+    if (d->counters_cap < need) {
+        (void)hipFree(d->counters);
+        d->counters = nullptr;
+        d->counters_cap = 0;
+        if (int rc = dev_alloc(&d->counters, (size_t)need + 1)) return rc;
+        d->counters_cap = need;
+    }
+    HIP_TRY(hipMemsetAsync(d->counters, 0, sizeof(unsigned long long) * need, s));
+    return LDPC_OK;
+}
+
+// The run's end: the counters to the host, once everything on stream s is done.
+int counters_read(ldpc_decoder *d, int n_points, int64_t *counters_out, hipStream_t s) {
+    const int need = n_points * LDPC_MC_NCOUNT;
+    std::vector<unsigned long long> h(need);
+    HIP_TRY(hipMemcpyAsync(h.data(), d->counters, sizeof(unsigned long long) * need, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int i = 0; i < need; ++i) counters_out[i] = (int64_t)h[i];
+    return LDPC_OK;
 }
 
 int ensure_phys_tile(ldpc_decoder *d, const DevGraph &P) {
@@ -875,8 +900,10 @@ int64_t ldpc_tile_lds_bytes(const ldpc_graph *g) {
 }
 
 namespace {
-bool phys_use_lds(const DevGraph &P, uint32_t flags);
+bool phys_use_lds(const DevGraph &P, uint32_t flags) {
+    return !(flags & LDPC_F_PHYS_HBM) && ldpc::phys_lds_bytes(P) <= kLdsLimit;
 }
+}  // namespace
 
 const char *ldpc_phys_kernel_name(const ldpc_graph *g, uint32_t flags) {
     if (!g) return "";
@@ -1417,15 +1444,7 @@ int ldpc_mc_run(ldpc_decoder *d, uint64_t seed, int32_t n_points, const double *
     if (int rc0 = ensure_messages(d)) return rc0;
     hipStream_t s = (hipStream_t)stream;
     const bool nllr = flags & LDPC_F_NLLR;
-    const int need = n_points * LDPC_MC_NCOUNT;
-    if (d->counters_cap < need) {
-        (void)hipFree(d->counters);
-        d->counters = nullptr;
-        d->counters_cap = 0;
-        if (int rc = dev_alloc(&d->counters, (size_t)need + 1)) return rc;
-        d->counters_cap = need;
-    }
-    HIP_TRY(hipMemsetAsync(d->counters, 0, sizeof(unsigned long long) * need, s));
+    if (int rc = counters_begin(d, n_points, s)) return rc;
     const int64_t cap = (int64_t)d->cap_tiles * kTile;
     if (!(flags & LDPC_F_STATIC)) {
         for (int p = 0; p < n_points; ++p)
@@ -1451,11 +1470,7 @@ int ldpc_mc_run(ldpc_decoder *d, uint64_t seed, int32_t n_points, const double *
             }
         }
     }
-    std::vector<unsigned long long> h(need);
-    HIP_TRY(hipMemcpyAsync(h.data(), d->counters, sizeof(unsigned long long) * need, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (int i = 0; i < need; ++i) counters_out[i] = (int64_t)h[i];
-    return LDPC_OK;
+    return counters_read(d, n_points, counters_out, s);
 }
 
 int ldpc_rare_rows_read(ldpc_decoder *d, int64_t *out) {
@@ -1600,44 +1615,42 @@ int phys_rule(const char *fn, const ldpc_graph *g, uint32_t flags, int32_t cn_ru
 
 int64_t ldpc_phys_lds_bytes(const ldpc_graph *g) { return g ? (int64_t)ldpc::phys_lds_bytes(g->dg) : -1; }
 
+extern "C++" {  // the function templates below cannot have C linkage
 namespace {
 
-int phys_decode_lds(const ldpc_graph *g, int32_t batch, const double *llr, int32_t max_iter, uint32_t flags,
-                    uint8_t *z_out, int32_t *conv_out, int32_t *status_out, int32_t *iters_out, float *post_out,
-                    hipStream_t s, const PhysRule &rule) {
-    const DevGraph &G = g->dg;
-    const size_t n = (size_t)G.n, B = (size_t)batch;
-    // flooding (any rule) or, with a layer table, the layered kernel
-    auto launch = [&](const double *in, uint8_t *z, int *conv, int *status, int *iters, float *post) {
-        if (rule.layer_ptr)
-            return ldpc::launch_phys_layered(G, in, nullptr, 0, batch, max_iter, z, conv, status, iters, post, nullptr,
-                                             nullptr, std::min(phys_layered_grid(G, rule), batch), s, rule);
-        return ldpc::launch_phys(G, in, nullptr, 0, batch, max_iter, z, conv, status, iters, post, nullptr, nullptr,
-                                 std::min(phys_grid(G), batch), s, rule);
-    };
+// A one-shot decode by one launch: `launch(llr, z, ints, post)` gets device
+// pointers, ints[k] the k-th of the per-frame integer outputs ints_out (3 or 4).
+// With LDPC_F_DEVICE_PTRS those are the caller's own; otherwise the LLRs are
+// staged up, and what the caller asked for (non-null) is copied back before a sync.
+template <class Post, class Launch>
+int phys_decode_staged(const char *fn, const DevGraph &G, int32_t batch, const double *llr, uint32_t flags,
+                       uint8_t *z_out, std::initializer_list<int32_t *> ints_out, Post *post_out, hipStream_t s,
+                       Launch &&launch) {
     if (flags & LDPC_F_DEVICE_PTRS) {
-        HIP_TRY(launch(llr, z_out, conv_out, status_out, iters_out, post_out));
+        HIP_TRY(launch(llr, z_out, ints_out.begin(), post_out));
         return LDPC_OK;
     }
+    const size_t n = (size_t)G.n, B = (size_t)batch, n_ints = ints_out.size();
     double *d_llr = nullptr;
     uint8_t *d_z = nullptr;
     int *d_i = nullptr;
-    float *d_post = nullptr;
+    Post *d_post = nullptr;
     int rc = dev_alloc(&d_llr, B * n);
     if (!rc) rc = dev_alloc(&d_z, B * n);
-    if (!rc) rc = dev_alloc(&d_i, 3 * B);
+    if (!rc) rc = dev_alloc(&d_i, n_ints * B);
     if (!rc && post_out) rc = dev_alloc(&d_post, B * n);
     hipError_t e = hipSuccess;
     if (!rc) {
+        int *const d_ints[4] = {d_i, d_i + B, d_i + 2 * B, d_i + 3 * B};  // n_ints of them exist
         e = hipMemcpyAsync(d_llr, llr, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
-        if (!e) e = launch(d_llr, d_z, d_i, d_i + B, d_i + 2 * B, d_post);
+        if (!e) e = launch(d_llr, d_z, d_ints, d_post);
         if (!e && z_out) e = hipMemcpyAsync(z_out, d_z, B * n, hipMemcpyDeviceToHost, s);
-        if (!e && conv_out) e = hipMemcpyAsync(conv_out, d_i, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (!e && status_out) e = hipMemcpyAsync(status_out, d_i + B, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (!e && iters_out) e = hipMemcpyAsync(iters_out, d_i + 2 * B, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (!e && post_out) e = hipMemcpyAsync(post_out, d_post, sizeof(float) * B * n, hipMemcpyDeviceToHost, s);
+        for (size_t k = 0; k < n_ints; ++k)
+            if (int32_t *out = ints_out.begin()[k]; !e && out)
+                e = hipMemcpyAsync(out, d_ints[k], sizeof(int) * B, hipMemcpyDeviceToHost, s);
+        if (!e && post_out) e = hipMemcpyAsync(post_out, d_post, sizeof(Post) * B * n, hipMemcpyDeviceToHost, s);
         if (!e) e = hipStreamSynchronize(s);
-        if (e) rc = ldpc_fail(LDPC_EDEVICE, "ldpc_phys_decode: %s", hipGetErrorString(e));
+        if (e) rc = ldpc_fail(LDPC_EDEVICE, "%s: %s", fn, hipGetErrorString(e));
     }
     (void)hipFree(d_llr);
     (void)hipFree(d_z);
@@ -1708,110 +1721,131 @@ void mc_stats_point(const ldpc_decoder *d, int p, int64_t frame_base, ldpc::McSt
     ms.max_iter = d->ms_T;
 }
 
-// The layered schedule on the tiles (phys_tile.hip): per iteration one launch
-// per layer, in order on the stream, then the syndrome of b = (L < 0) and the
-// exits -- on the device every iteration, so the results never depend on the
-// polls.  The host polls and compacts as phys_tile_decode does; the exit of
-// iteration max_iter - 1 stops the frames still running (no final sweep).
-int phys_tile_decode_layered(ldpc_decoder *d, const DevGraph &P, int max_iter, bool from_ch, hipStream_t s,
-                             unsigned long long *ctr, const PhysRule &rule, const ldpc::McStats &ms) {
+// Decode the frames bound in d->st with HBM-resident tile kernels, a family's
+// own behind `ops` (PhysTileOps, QTileOps): up to max_iter sweeps, then what
+// the family needs to finish.  The host reads the running-tile and
+// running-frame counts after sweep(it) for it < 4 and every 4th iteration
+// after, and stops issuing sweeps once they are zero.  With ops.ctr (a
+// Monte-Carlo run: only the counters leave the device) the running frames are
+// compacted into the first tiles once at most a quarter of the launched slots
+// hold them, the finished frames counted into ctr first (phys_tile.hip), and
+// the rest at the end.  ops.st is the family's copy of d->st: its ntiles
+// shrinks with each compaction.
+template <class Ops>
+int phys_tile_sweeps(ldpc_decoder *d, int max_iter, hipStream_t s, Ops &&ops) {
     if (int rc = ensure_pactive(d, max_iter)) return rc;
-    DevState st = d->st;  // st.ntiles shrinks with each compaction
-    const PhysTile pt = phys_tile(d);
     const int cap = d->cap_tiles * kTile;
     const bool compact = phys_compact_enabled();
     HIP_TRY(hipMemsetAsync(d->pactive, 0, sizeof(int) * 2 * max_iter, s));
-    HIP_TRY(ldpc::launch_phys_tile_init(P, st, pt, from_ch, s));
+    HIP_TRY(ops.init());
     for (int it = 0; it < max_iter; ++it) {
-        HIP_TRY(timed(d, LDPC_K_PHYS_CN, s, [&] {
-            for (int l = 0; l < rule.n_layers; ++l) {
-                const int lbeg = rule.h_layer_ptr[l], lrows = rule.h_layer_ptr[l + 1] - lbeg;
-                if (hipError_t e = ldpc::launch_phys_layer_tile(P, st, pt, it, lbeg, lrows, s, rule)) return e;
-            }
-            return hipSuccess;
-        }));
-        HIP_TRY(timed(d, LDPC_K_PHYS_VN, s,
-                      [&] { return ldpc::launch_phys_layer_exit(P, st, pt, it, d->pactive, max_iter, s); }));
+        HIP_TRY(ops.sweep(it));
         if (it + 1 < max_iter && (it < 4 || (it + 1) % 4 == 0)) {
-            int running[2] = {0, 0};  // tiles, frames
-            HIP_TRY(hipMemcpyAsync(&running[0], d->pactive + it, sizeof(int), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(&running[1], d->pactive + max_iter + it, sizeof(int), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            if (running[0] == 0) break;  // every frame has stopped
-            const int nt = (running[1] + kTile - 1) / kTile;
-            if (ctr && compact && nt < st.ntiles && 4 * (int64_t)running[1] <= (int64_t)st.ntiles * kTile) {
-                if (!d->cpairs && dev_alloc(&d->cpairs, 1 + 2 * (size_t)cap)) return LDPC_ENOMEM;
-                HIP_TRY(timed(d, LDPC_K_COUNT, s, [&] { return ldpc::launch_phys_tile_count(P, st, pt, ctr, s, ms); }));
-                HIP_TRY(ldpc::launch_phys_compact(P, st, pt, nt, cap, d->cpairs, s, ms.hist ? ms.slot_frame : nullptr));
-                st.ntiles = nt;
-            }
-        }
-    }
-    return LDPC_OK;
-}
-
-// Decode the frames bound in d->st (channel LLRs in d->ch) on graph P with the
-// HBM-resident tile kernels: up to max_iter CN+VN sweeps, then a syndrome-only
-// sweep.  The host reads the running-tile and running-frame counts after
-// VN(it) for it < 4 and every 4th iteration after, and stops issuing sweeps
-// once they are zero.  With ctr (a Monte-Carlo run: only the counters leave
-// the device) the running frames are compacted into the first tiles once at
-// most a quarter of the launched slots hold them, the finished frames counted
-// into ctr first (phys_tile.hip).
-int phys_tile_decode(ldpc_decoder *d, const DevGraph &P, int max_iter, bool from_ch, hipStream_t s,
-                     unsigned long long *ctr = nullptr, const PhysRule &rule = PhysRule{},
-                     const ldpc::McStats &ms = ldpc::McStats{}) {
-    if (rule.layer_ptr) return phys_tile_decode_layered(d, P, max_iter, from_ch, s, ctr, rule, ms);
-    if (int rc = ensure_pactive(d, max_iter)) return rc;
-    DevState st = d->st;  // st.ntiles shrinks with each compaction
-    const PhysTile pt = phys_tile(d);
-    const int cap = d->cap_tiles * kTile;
-    const bool compact = phys_compact_enabled();
-    HIP_TRY(hipMemsetAsync(d->pactive, 0, sizeof(int) * 2 * max_iter, s));
-    HIP_TRY(ldpc::launch_phys_tile_init(P, st, pt, from_ch, s));
-    for (int it = 0; it < max_iter; ++it) {
-        HIP_TRY(timed(d, LDPC_K_PHYS_CN, s, [&] { return ldpc::launch_phys_tile_cn(P, st, pt, it, false, s, rule); }));
-        HIP_TRY(timed(d, LDPC_K_PHYS_VN, s,
-                      [&] { return ldpc::launch_phys_tile_vn(P, st, pt, it, d->pactive, max_iter, s); }));
-        if (it + 1 < max_iter && (it < 4 || (it + 1) % 4 == 0)) {
-            // iterations 1 and 2: the frames whose posterior already
+            // iterations 1 and 2 (flooding): the frames whose posterior already
             // satisfies every check stop now instead of after the next CN
             // sweep (DVB-S2 profile at 1 dB, 2 iterations per frame: +25 %).
             // Each early syndrome costs ~1 ms on 128 tiles, more than it saves
             // where frames stop after 20-40 iterations (the -2.5 dB
             // waterfall: -1.4 % with it at every poll of it < 4,
             // profiles/r5_ab/r5ao_ab)
-            if (it == 1 || it == 2)
-                HIP_TRY(timed(d, LDPC_K_PHYS_VN, s, [&] {
-                    return ldpc::launch_phys_tile_early_exit(P, st, pt, it, d->pactive, max_iter, s);
-                }));
+            if (ops.has_early_exit && (it == 1 || it == 2))
+                HIP_TRY(timed(d, LDPC_K_PHYS_VN, s, [&] { return ops.early_exit(it); }));
             int running[2] = {0, 0};  // tiles, frames
             HIP_TRY(hipMemcpyAsync(&running[0], d->pactive + it, sizeof(int), hipMemcpyDeviceToHost, s));
             HIP_TRY(hipMemcpyAsync(&running[1], d->pactive + max_iter + it, sizeof(int), hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
-            if (running[0] == 0) break;  // every frame has stopped (converged; final() leaves them alone)
+            if (running[0] == 0) break;  // every frame has stopped (converged; finish() leaves them alone)
             const int nt = (running[1] + kTile - 1) / kTile;
             // (a quarter: half measured the same, profiles/r5_ab/r5am_ab)
-            if (ctr && compact && nt < st.ntiles && 4 * (int64_t)running[1] <= (int64_t)st.ntiles * kTile) {
+            if (ops.ctr && compact && nt < ops.st.ntiles &&
+                4 * (int64_t)running[1] <= (int64_t)ops.st.ntiles * kTile) {
                 if (!d->cpairs && dev_alloc(&d->cpairs, 1 + 2 * (size_t)cap)) return LDPC_ENOMEM;
-                HIP_TRY(timed(d, LDPC_K_COUNT, s, [&] { return ldpc::launch_phys_tile_count(P, st, pt, ctr, s, ms); }));
-                HIP_TRY(ldpc::launch_phys_compact(P, st, pt, nt, cap, d->cpairs, s, ms.hist ? ms.slot_frame : nullptr));
-                st.ntiles = nt;
+                HIP_TRY(timed(d, LDPC_K_COUNT, s, [&] { return ops.count(); }));
+                HIP_TRY(ops.compact(nt));
+                ops.st.ntiles = nt;
             }
         }
     }
-    HIP_TRY(ldpc::launch_phys_tile_cn(P, st, pt, max_iter, true, s, rule));
-    HIP_TRY(ldpc::launch_phys_tile_final(P, st, pt, max_iter, s));
+    HIP_TRY(ops.finish());
+    if (ops.ctr) {  // the frames no compaction counted, over all of the chunk's tiles again
+        ops.st.ntiles = d->st.ntiles;
+        HIP_TRY(timed(d, LDPC_K_COUNT, s, [&] { return ops.count(); }));
+    }
     return LDPC_OK;
 }
 
-bool phys_use_lds(const DevGraph &P, uint32_t flags) {
-    return !(flags & LDPC_F_PHYS_HBM) && ldpc::phys_lds_bytes(P) <= kLdsLimit;
+// phys_tile_sweeps on the fp32 tile kernels (phys_tile.hip), channel LLRs in
+// d->ch (from_ch) or the generator's Lambda tiles.  Flooding: a CN and a VN
+// sweep per iteration, then a syndrome-only sweep and final().  Layered: per
+// iteration one launch per layer, in order on the stream, then the syndrome of
+// b = (L < 0) and the exits -- on the device every iteration, so the results
+// never depend on the polls; the exit of iteration max_iter - 1 stops the
+// frames still running (no final sweep).
+struct PhysTileOps {
+    ldpc_decoder *d;
+    const DevGraph &P;
+    DevState st;
+    PhysTile pt;
+    int max_iter;
+    bool from_ch;
+    hipStream_t s;
+    unsigned long long *ctr;
+    const PhysRule &rule;
+    const ldpc::McStats &ms;
+    const bool has_early_exit = !rule.layer_ptr;  // flooding only
+
+    hipError_t init() { return ldpc::launch_phys_tile_init(P, st, pt, from_ch, s); }
+    hipError_t layers(int it) {
+        for (int l = 0; l < rule.n_layers; ++l) {
+            const int lbeg = rule.h_layer_ptr[l], lrows = rule.h_layer_ptr[l + 1] - lbeg;
+            if (hipError_t e = ldpc::launch_phys_layer_tile(P, st, pt, it, lbeg, lrows, s, rule)) return e;
+        }
+        return hipSuccess;
+    }
+    hipError_t sweep(int it) {
+        if (hipError_t e = timed(d, LDPC_K_PHYS_CN, s, [&] {
+                return rule.layer_ptr ? layers(it) : ldpc::launch_phys_tile_cn(P, st, pt, it, false, s, rule);
+            }))
+            return e;
+        return timed(d, LDPC_K_PHYS_VN, s, [&] {
+            return rule.layer_ptr ? ldpc::launch_phys_layer_exit(P, st, pt, it, d->pactive, max_iter, s)
+                                  : ldpc::launch_phys_tile_vn(P, st, pt, it, d->pactive, max_iter, s);
+        });
+    }
+    hipError_t early_exit(int it) {
+        return ldpc::launch_phys_tile_early_exit(P, st, pt, it, d->pactive, max_iter, s);
+    }
+    hipError_t count() { return ldpc::launch_phys_tile_count(P, st, pt, ctr, s, ms); }
+    hipError_t compact(int nt) {
+        return ldpc::launch_phys_compact(P, st, pt, nt, d->cap_tiles * kTile, d->cpairs, s,
+                                         ms.hist ? ms.slot_frame : nullptr);
+    }
+    hipError_t finish() {
+        if (rule.layer_ptr) return hipSuccess;
+        if (hipError_t e = ldpc::launch_phys_tile_cn(P, st, pt, max_iter, true, s, rule)) return e;
+        return ldpc::launch_phys_tile_final(P, st, pt, max_iter, s);
+    }
+};
+
+int phys_tile_decode(ldpc_decoder *d, const DevGraph &P, int max_iter, bool from_ch, hipStream_t s,
+                     unsigned long long *ctr, const PhysRule &rule, const ldpc::McStats &ms = ldpc::McStats{}) {
+    return phys_tile_sweeps(d, max_iter, s,
+                            PhysTileOps{d, P, d->st, phys_tile(d), max_iter, from_ch, s, ctr, rule, ms});
 }
 
-int phys_decode_tile(const ldpc_graph *g, int32_t batch, const double *llr, int32_t max_iter, uint32_t flags,
-                     uint8_t *z_out, int32_t *conv_out, int32_t *status_out, int32_t *iters_out, float *post_out,
-                     hipStream_t s, const PhysRule &rule) {
+// Whether a rule phys_rule filled runs one LDS kernel on graph P, not the HBM tile kernels.
+bool phys_on_lds(const PhysRule &rule, const DevGraph &P, uint32_t flags) {
+    return rule.layer_ptr ? !rule.layered_tile : phys_use_lds(P, flags);
+}
+
+// A one-shot decode on the tiles: chunks of 1024 frames through a temporary
+// decoder's workspace and staging.  `decode(d)` decodes the chunk bound in
+// d->st (channel LLRs in d->ch) and returns an rc; `out(d, z, post)` launches
+// the kernel that writes the hard decisions and posteriors to device memory.
+template <class Post, class Decode, class Out>
+int phys_decode_chunks(const ldpc_graph *g, int32_t batch, const double *llr, uint32_t flags, uint8_t *z_out,
+                       int32_t *conv_out, int32_t *status_out, int32_t *iters_out, Post *post_out, hipStream_t s,
+                       Decode &&decode, Out &&out) {
     const DevGraph &G = g->dg;
     const bool dev_ptrs = flags & LDPC_F_DEVICE_PTRS;
     const int chunk = std::min<int>(batch, 1024);
@@ -1833,10 +1867,10 @@ int phys_decode_tile(const ldpc_graph *g, int32_t batch, const double *llr, int3
             src = d->llr_stage;
         }
         HIP_TRY(ldpc::launch_load_llr(G, st, src, s));
-        if (int rc = phys_tile_decode(d, G, max_iter, true, s, nullptr, rule)) return rc;
+        if (int rc = decode(d)) return rc;
         uint8_t *zd = z_out ? (dev_ptrs ? z_out + (size_t)start * n : d->z_stage) : nullptr;
-        float *pd = post_out ? (dev_ptrs ? post_out + (size_t)start * n : (float *)d->post_stage) : nullptr;
-        HIP_TRY(ldpc::launch_phys_tile_out(G, st, phys_tile(d), zd, pd, s));
+        Post *pd = post_out ? (dev_ptrs ? post_out + (size_t)start * n : (Post *)d->post_stage) : nullptr;
+        HIP_TRY(out(d, zd, pd));
         const hipMemcpyKind kind = dev_ptrs ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
         if (conv_out) HIP_TRY(hipMemcpyAsync(conv_out + start, st.conv, sizeof(int) * cnt, kind, s));
         if (status_out) HIP_TRY(hipMemcpyAsync(status_out + start, st.status, sizeof(int) * cnt, kind, s));
@@ -1844,17 +1878,13 @@ int phys_decode_tile(const ldpc_graph *g, int32_t batch, const double *llr, int3
         if (!dev_ptrs) {
             if (z_out) HIP_TRY(hipMemcpyAsync(z_out + (size_t)start * n, zd, cnt * n, hipMemcpyDeviceToHost, s));
             if (post_out)
-                HIP_TRY(hipMemcpyAsync(post_out + (size_t)start * n, pd, sizeof(float) * cnt * n,
+                HIP_TRY(hipMemcpyAsync(post_out + (size_t)start * n, pd, sizeof(Post) * cnt * n,
                                        hipMemcpyDeviceToHost, s));
         }
         HIP_TRY(hipStreamSynchronize(s));  // staging and workspace are reused / freed
     }
     return LDPC_OK;
 }
-
-}  // namespace
-
-namespace {
 
 int phys_decode_any(const char *fn, const ldpc_graph *g, int32_t batch, const double *llr, int32_t max_iter,
                     uint32_t flags, int32_t cn_rule, int32_t schedule, float param, uint8_t *z_out, int32_t *conv_out,
@@ -1867,15 +1897,30 @@ int phys_decode_any(const char *fn, const ldpc_graph *g, int32_t batch, const do
     if (int rc = phys_rule(fn, g, flags, cn_rule, schedule, param, &rule)) return rc;
     if (batch == 0) return LDPC_OK;
     hipStream_t s = (hipStream_t)stream;
-    if (rule.layer_ptr ? !rule.layered_tile : phys_use_lds(g->dg, flags))
-        return phys_decode_lds(g, batch, llr, max_iter, flags, z_out, conv_out, status_out, iters_out, post_out, s,
-                               rule);
-    return phys_decode_tile(g, batch, llr, max_iter, flags, z_out, conv_out, status_out, iters_out, post_out, s, rule);
+    const DevGraph &G = g->dg;
+    if (phys_on_lds(rule, G, flags))  // flooding (any rule) or, with a layer table, the layered kernel
+        return phys_decode_staged(
+            fn, G, batch, llr, flags, z_out, {conv_out, status_out, iters_out}, post_out, s,
+            [&](const double *in, uint8_t *z, int *const *iv, float *post) {
+                if (rule.layer_ptr)
+                    return ldpc::launch_phys_layered(G, in, nullptr, 0, batch, max_iter, z, iv[0], iv[1], iv[2], post,
+                                                     nullptr, nullptr, std::min(phys_layered_grid(G, rule), batch), s,
+                                                     rule);
+                return ldpc::launch_phys(G, in, nullptr, 0, batch, max_iter, z, iv[0], iv[1], iv[2], post, nullptr,
+                                         nullptr, std::min(phys_grid(G), batch), s, rule);
+            });
+    return phys_decode_chunks(
+        g, batch, llr, flags, z_out, conv_out, status_out, iters_out, post_out, s,
+        [&](ldpc_decoder *d) { return phys_tile_decode(d, G, max_iter, true, s, nullptr, rule); },
+        [&](ldpc_decoder *d, uint8_t *z, float *post) {
+            return ldpc::launch_phys_tile_out(G, d->st, phys_tile(d), z, post, s);
+        });
 }
 
-int phys_mc_any(const char *fn, ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int32_t n_points,
-                const double *sigmas, int64_t frames_per_point, int64_t frame0, int32_t max_iter, uint32_t flags,
-                int32_t cn_rule, int32_t schedule, float param, int64_t *counters_out, void *stream) {
+// The argument checks every physical-mode Monte-Carlo entry shares; they touch
+// no device.  d decodes graph gp (P below) on frames of its own graph (G).
+int phys_mc_check(const char *fn, const ldpc_decoder *d, const ldpc_graph *gp, int32_t n_points, const double *sigmas,
+                  int64_t frames_per_point, int64_t frame0, int32_t max_iter, const int64_t *counters_out) {
     if (!gp) return ldpc_fail(LDPC_EINVAL, "%s: NULL graph", fn);
     if (!d || n_points <= 0 || !sigmas || frames_per_point < 0 || frame0 < 0 || max_iter < 1 || !counters_out)
         return ldpc_fail(LDPC_EINVAL, "%s: bad arguments", fn);
@@ -1889,29 +1934,27 @@ int phys_mc_any(const char *fn, ldpc_decoder *d, const ldpc_graph *gp, uint64_t 
         return ldpc_fail(LDPC_EINVAL, "%s: physical graph shape %dx%d != %dx%d", fn, P.m, P.n, G.m, G.n);
     for (int p = 0; p < n_points; ++p)
         if (!(sigmas[p] > 0.0)) return ldpc_fail(LDPC_EINVAL, "%s: sigma[%d] <= 0", fn, p);
-    if (int rc = channel_frames_check(fn, d, 0)) return rc;
-    DeviceGuard dg(d->g->device);
-    PhysRule rule;
-    if (int rc = phys_rule(fn, gp, flags, cn_rule, schedule, param, &rule)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const bool lds = rule.layer_ptr ? !rule.layered_tile : phys_use_lds(P, flags);
-    if (!lds)
-        if (int rc = ensure_phys_tile(d, P)) return rc;
+    return channel_frames_check(fn, d, 0);
+}
+
+// A physical-mode Monte-Carlo run on a decoder phys_mc_check passed, its
+// device current, in chunks of the decoder's capacity.  The frames go straight
+// to the family's decoder as fp32 Lambda: kFramesRowLambda (rows, contiguous
+// per frame) for an LDS kernel, kFramesTileLambda (pLam) for the HBM tile
+// kernels (tiles).  `chunk(st, cnt, rows, ctr, ms)` decodes the cnt frames
+// bound in st and counts them into the point's counters ctr; it returns an rc.
+template <class Chunk>
+int phys_mc_drive(ldpc_decoder *d, uint64_t seed, int32_t n_points, const double *sigmas, int64_t frames_per_point,
+                  int64_t frame0, int32_t max_iter, int64_t *counters_out, hipStream_t s, ldpc::FramesOut layout,
+                  bool tiles, Chunk &&chunk) {
+    const DevGraph &G = d->g->dg;
     if (int rc = ensure_pbits(d, G)) return rc;
     ldpc::RateMatchDev rm;
     if (int rc = rate_match_dev(d, s, &rm)) return rc;
     ldpc::HarqDev hq;
     if (int rc = harq_dev(d, s, &hq)) return rc;
-    const int need = n_points * LDPC_MC_NCOUNT;
-    if (d->counters_cap < need) {
-        (void)hipFree(d->counters);
-        d->counters = nullptr;
-        d->counters_cap = 0;
-        if (int rc = dev_alloc(&d->counters, (size_t)need + 1)) return rc;
-        d->counters_cap = need;
-    }
-    HIP_TRY(hipMemsetAsync(d->counters, 0, sizeof(unsigned long long) * need, s));
-    if (int rc = mc_stats_begin(d, n_points, max_iter, !lds, s)) return rc;
+    if (int rc = counters_begin(d, n_points, s)) return rc;
+    if (int rc = mc_stats_begin(d, n_points, max_iter, tiles, s)) return rc;
     const int64_t cap = (int64_t)d->cap_tiles * kTile;
     for (int p = 0; p < n_points; ++p) {
         unsigned long long *ctr = d->counters + (size_t)p * LDPC_MC_NCOUNT;
@@ -1921,40 +1964,52 @@ int phys_mc_any(const char *fn, ldpc_decoder *d, const ldpc_graph *gp, uint64_t 
             const DevState st = d->st;
             ldpc::McStats ms;
             mc_stats_point(d, p, frame0 + start, &ms);
-            // frames go straight to the decoder's fp32 Lambda: tile layout for the
-            // HBM tile decoder, row-major (contiguous per frame) for the LDS decoder
             float *rows = (float *)d->llr_stage;  // cap x n doubles: room for cap x n floats
             HIP_TRY(timed(d, LDPC_K_GEN, s, [&] {
-                return ldpc::launch_frames(G, st, phys_tile(d), seed, p, sigmas[p], frame0 + start,
-                                           lds ? ldpc::kFramesRowLambda : ldpc::kFramesTileLambda, rows, d->chan, s,
-                                           rm, hq);
+                return ldpc::launch_frames(G, st, phys_tile(d), seed, p, sigmas[p], frame0 + start, layout, rows,
+                                           d->chan, s, rm, hq);
             }));
-            if (lds) {
-                HIP_TRY(timed(d, LDPC_K_PHYS, s, [&] {
-                    if (rule.layer_ptr)
-                        return ldpc::launch_phys_layered(P, nullptr, rows, 2, cnt, max_iter, nullptr, nullptr, nullptr,
-                                                         nullptr, nullptr, st.ubits, ctr,
-                                                         std::min(phys_layered_grid(P, rule), cnt), s, rule, ms);
-                    return ldpc::launch_phys(P, nullptr, rows, 2, cnt, max_iter, nullptr, nullptr, nullptr, nullptr,
-                                             nullptr, st.ubits, ctr, std::min(phys_grid(P), cnt), s, rule, ms);
-                }));
-            } else {
-                if (ms.hist) HIP_TRY(ldpc::launch_mc_stats_slots(ms.slot_frame, ms.frame_base, cnt, s));
-                if (int rc = phys_tile_decode(d, P, max_iter, false, s, ctr, rule, ms)) return rc;
-                HIP_TRY(timed(d, LDPC_K_COUNT, s,
-                              [&] { return ldpc::launch_phys_tile_count(P, st, phys_tile(d), ctr, s, ms); }));
-            }
+            if (tiles && ms.hist) HIP_TRY(ldpc::launch_mc_stats_slots(ms.slot_frame, ms.frame_base, cnt, s));
+            if (int rc = chunk(st, cnt, rows, ctr, ms)) return rc;
         }
     }
-    std::vector<unsigned long long> h(need);
-    HIP_TRY(hipMemcpyAsync(h.data(), d->counters, sizeof(unsigned long long) * need, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (int i = 0; i < need; ++i) counters_out[i] = (int64_t)h[i];
+    if (int rc = counters_read(d, n_points, counters_out, s)) return rc;
     if (d->ms_on) d->ms_state = 1;
     return LDPC_OK;
 }
 
+int phys_mc_any(const char *fn, ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int32_t n_points,
+                const double *sigmas, int64_t frames_per_point, int64_t frame0, int32_t max_iter, uint32_t flags,
+                int32_t cn_rule, int32_t schedule, float param, int64_t *counters_out, void *stream) {
+    if (int rc = phys_mc_check(fn, d, gp, n_points, sigmas, frames_per_point, frame0, max_iter, counters_out))
+        return rc;
+    const DevGraph &P = gp->dg;
+    DeviceGuard dg(d->g->device);
+    PhysRule rule;
+    if (int rc = phys_rule(fn, gp, flags, cn_rule, schedule, param, &rule)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const bool lds = phys_on_lds(rule, P, flags);
+    if (!lds)
+        if (int rc = ensure_phys_tile(d, P)) return rc;
+    return phys_mc_drive(
+        d, seed, n_points, sigmas, frames_per_point, frame0, max_iter, counters_out, s,
+        lds ? ldpc::kFramesRowLambda : ldpc::kFramesTileLambda, !lds,
+        [&](const DevState &st, int cnt, const float *rows, unsigned long long *ctr, const ldpc::McStats &ms) -> int {
+            if (!lds) return phys_tile_decode(d, P, max_iter, false, s, ctr, rule, ms);
+            HIP_TRY(timed(d, LDPC_K_PHYS, s, [&] {
+                if (rule.layer_ptr)
+                    return ldpc::launch_phys_layered(P, nullptr, rows, 2, cnt, max_iter, nullptr, nullptr, nullptr,
+                                                     nullptr, nullptr, st.ubits, ctr,
+                                                     std::min(phys_layered_grid(P, rule), cnt), s, rule, ms);
+                return ldpc::launch_phys(P, nullptr, rows, 2, cnt, max_iter, nullptr, nullptr, nullptr, nullptr,
+                                         nullptr, st.ubits, ctr, std::min(phys_grid(P), cnt), s, rule, ms);
+            }));
+            return LDPC_OK;
+        });
+}
+
 }  // namespace
+}  // extern "C++"
 
 int ldpc_phys_decode(const ldpc_graph *g, int32_t batch, const double *llr, int32_t max_iter, uint32_t flags,
                      uint8_t *z_out, int32_t *conv_out, int32_t *status_out, int32_t *iters_out, float *post_out,
@@ -2134,112 +2189,61 @@ ldpc::QTile quant_tile(ldpc_decoder *d, const ldpc::QuantRule &rule) {
     return qt;
 }
 
-// Decode the frames bound in d->st on graph P with the fixed-point tile
-// kernels (phys_qtile.hip); lam32: the generator's fp32 Lambda tiles, or null:
-// the channel LLRs in d->ch.  The launches, the polls (it < 4 and every 4th
-// iteration) and, with ctr, the compaction are phys_tile_decode's and
-// phys_tile_decode_layered's; the exits run on the device every iteration, so
-// no result depends on a poll.
+// phys_tile_sweeps on the fixed-point tile kernels (phys_qtile.hip); lam32:
+// the generator's fp32 Lambda tiles, or null: the channel LLRs in d->ch.
+// Sweeps and exits as PhysTileOps for either schedule; flooding ends with
+// final() alone (the frames that converge on the last iteration; the layered
+// exit stops every frame itself).
+struct QTileOps {
+    ldpc_decoder *d;
+    const DevGraph &P;
+    DevState st;
+    ldpc::QTile qt;
+    int max_iter;
+    const float *lam32;
+    hipStream_t s;
+    unsigned long long *ctr;
+    const ldpc::QuantRule &rule;
+    const ldpc::McStats &ms;
+    const bool has_early_exit = !rule.layer_ptr;  // flooding only
+
+    hipError_t init() { return ldpc::launch_phys_qtile_init(P, st, qt, lam32, !rule.layer_ptr, s); }
+    hipError_t layers(int it) {
+        for (int l = 0; l < rule.n_layers; ++l) {
+            const int lbeg = rule.h_layer_ptr[l], lrows = rule.h_layer_ptr[l + 1] - lbeg;
+            if (hipError_t e = ldpc::launch_phys_qlayer_tile(P, st, qt, rule.cn, it, lbeg, lrows, rule.layer_rows, s))
+                return e;
+        }
+        return hipSuccess;
+    }
+    hipError_t sweep(int it) {
+        if (hipError_t e = timed(d, LDPC_K_PHYS_CN, s, [&] {
+                return rule.layer_ptr ? layers(it) : ldpc::launch_phys_qtile_cn(P, st, qt, rule.cn, it, s);
+            }))
+            return e;
+        return timed(d, LDPC_K_PHYS_VN, s, [&] {
+            return rule.layer_ptr ? ldpc::launch_phys_qlayer_exit(P, st, qt, it, d->pactive, max_iter, s)
+                                  : ldpc::launch_phys_qtile_vn(P, st, qt, it, d->pactive, max_iter, s);
+        });
+    }
+    hipError_t early_exit(int it) {
+        return ldpc::launch_phys_qtile_early_exit(P, st, qt, it, d->pactive, max_iter, s);
+    }
+    hipError_t count() { return ldpc::launch_phys_qtile_count(P, st, qt, ctr, s, ms); }
+    hipError_t compact(int nt) {
+        return ldpc::launch_phys_qtile_compact(P, st, qt, !rule.layer_ptr, nt, d->cap_tiles * kTile, d->cpairs, s,
+                                               ms.hist ? ms.slot_frame : nullptr);
+    }
+    hipError_t finish() {
+        return rule.layer_ptr ? hipSuccess : ldpc::launch_phys_qtile_final(P, st, qt, max_iter, s);
+    }
+};
+
 int phys_qtile_decode(ldpc_decoder *d, const DevGraph &P, int max_iter, const float *lam32, hipStream_t s,
                       unsigned long long *ctr, const ldpc::QuantRule &rule,
                       const ldpc::McStats &ms = ldpc::McStats{}) {
-    if (int rc = ensure_pactive(d, max_iter)) return rc;
-    DevState st = d->st;  // st.ntiles shrinks with each compaction
-    const ldpc::QTile qt = quant_tile(d, rule);
-    const bool layered = rule.layer_ptr != nullptr;
-    const int cap = d->cap_tiles * kTile;
-    const bool compact = phys_compact_enabled();
-    HIP_TRY(hipMemsetAsync(d->pactive, 0, sizeof(int) * 2 * max_iter, s));
-    HIP_TRY(ldpc::launch_phys_qtile_init(P, st, qt, lam32, !layered, s));
-    for (int it = 0; it < max_iter; ++it) {
-        if (layered) {
-            HIP_TRY(timed(d, LDPC_K_PHYS_CN, s, [&] {
-                for (int l = 0; l < rule.n_layers; ++l) {
-                    const int lbeg = rule.h_layer_ptr[l], lrows = rule.h_layer_ptr[l + 1] - lbeg;
-                    if (hipError_t e = ldpc::launch_phys_qlayer_tile(P, st, qt, rule.cn, it, lbeg, lrows,
-                                                                     rule.layer_rows, s))
-                        return e;
-                }
-                return hipSuccess;
-            }));
-            HIP_TRY(timed(d, LDPC_K_PHYS_VN, s,
-                          [&] { return ldpc::launch_phys_qlayer_exit(P, st, qt, it, d->pactive, max_iter, s); }));
-        } else {
-            HIP_TRY(timed(d, LDPC_K_PHYS_CN, s, [&] { return ldpc::launch_phys_qtile_cn(P, st, qt, rule.cn, it, s); }));
-            HIP_TRY(timed(d, LDPC_K_PHYS_VN, s,
-                          [&] { return ldpc::launch_phys_qtile_vn(P, st, qt, it, d->pactive, max_iter, s); }));
-        }
-        if (it + 1 < max_iter && (it < 4 || (it + 1) % 4 == 0)) {
-            // flooding, iterations 1 and 2: the frames whose posterior satisfies
-            // every check stop now, not after the next check sweep (phys_tile_decode)
-            if (!layered && (it == 1 || it == 2))
-                HIP_TRY(timed(d, LDPC_K_PHYS_VN, s, [&] {
-                    return ldpc::launch_phys_qtile_early_exit(P, st, qt, it, d->pactive, max_iter, s);
-                }));
-            int running[2] = {0, 0};  // tiles, frames
-            HIP_TRY(hipMemcpyAsync(&running[0], d->pactive + it, sizeof(int), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(&running[1], d->pactive + max_iter + it, sizeof(int), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            if (running[0] == 0) break;  // every frame has stopped
-            const int nt = (running[1] + kTile - 1) / kTile;
-            if (ctr && compact && nt < st.ntiles && 4 * (int64_t)running[1] <= (int64_t)st.ntiles * kTile) {
-                if (!d->cpairs && dev_alloc(&d->cpairs, 1 + 2 * (size_t)cap)) return LDPC_ENOMEM;
-                HIP_TRY(timed(d, LDPC_K_COUNT, s,
-                              [&] { return ldpc::launch_phys_qtile_count(P, st, qt, ctr, s, ms); }));
-                HIP_TRY(ldpc::launch_phys_qtile_compact(P, st, qt, !layered, nt, cap, d->cpairs, s,
-                                                        ms.hist ? ms.slot_frame : nullptr));
-                st.ntiles = nt;
-            }
-        }
-    }
-    // flooding: the frames that converge on the last iteration (the layered exit stops every frame itself)
-    if (!layered) HIP_TRY(ldpc::launch_phys_qtile_final(P, st, qt, max_iter, s));
-    return LDPC_OK;
-}
-
-// ldpc_phys_decode_q on the tiles: chunks of 1024 frames through a temporary
-// workspace, staging as phys_decode_tile, int16 posteriors.
-int phys_decode_qtile(const ldpc_graph *g, int32_t batch, const double *llr, int32_t max_iter, uint32_t flags,
-                      uint8_t *z_out, int32_t *conv_out, int32_t *status_out, int32_t *iters_out, int16_t *post_out,
-                      hipStream_t s, const ldpc::QuantRule &rule) {
-    const DevGraph &G = g->dg;
-    const bool dev_ptrs = flags & LDPC_F_DEVICE_PTRS;
-    const int chunk = std::min<int>(batch, 1024);
-    ldpc_decoder *d = nullptr;
-    if (int rc = ldpc_decoder_create(g, chunk, &d)) return rc;
-    struct Free {
-        ldpc_decoder *d;
-        ~Free() { ldpc_decoder_destroy(d); }
-    } guard{d};
-    if (int rc = ensure_phys_tile(d, G)) return rc;
-    const size_t n = (size_t)G.n;
-    for (int start = 0; start < batch; start += chunk) {
-        const int cnt = std::min(chunk, batch - start);
-        state_bind(d, (cnt + kTile - 1) / kTile, cnt);
-        const DevState &st = d->st;
-        const double *src = llr + (size_t)start * n;
-        if (!dev_ptrs) {
-            HIP_TRY(hipMemcpyAsync(d->llr_stage, src, sizeof(double) * cnt * n, hipMemcpyHostToDevice, s));
-            src = d->llr_stage;
-        }
-        HIP_TRY(ldpc::launch_load_llr(G, st, src, s));
-        if (int rc = phys_qtile_decode(d, G, max_iter, nullptr, s, nullptr, rule)) return rc;
-        uint8_t *zd = z_out ? (dev_ptrs ? z_out + (size_t)start * n : d->z_stage) : nullptr;
-        int16_t *pd = post_out ? (dev_ptrs ? post_out + (size_t)start * n : (int16_t *)d->post_stage) : nullptr;
-        HIP_TRY(ldpc::launch_phys_qtile_out(G, st, quant_tile(d, rule), zd, pd, s));
-        const hipMemcpyKind kind = dev_ptrs ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-        if (conv_out) HIP_TRY(hipMemcpyAsync(conv_out + start, st.conv, sizeof(int) * cnt, kind, s));
-        if (status_out) HIP_TRY(hipMemcpyAsync(status_out + start, st.status, sizeof(int) * cnt, kind, s));
-        if (iters_out) HIP_TRY(hipMemcpyAsync(iters_out + start, st.iters, sizeof(int) * cnt, kind, s));
-        if (!dev_ptrs) {
-            if (z_out) HIP_TRY(hipMemcpyAsync(z_out + (size_t)start * n, zd, cnt * n, hipMemcpyDeviceToHost, s));
-            if (post_out)
-                HIP_TRY(hipMemcpyAsync(post_out + (size_t)start * n, pd, sizeof(int16_t) * cnt * n,
-                                       hipMemcpyDeviceToHost, s));
-        }
-        HIP_TRY(hipStreamSynchronize(s));  // staging and workspace are reused / freed
-    }
-    return LDPC_OK;
+    return phys_tile_sweeps(d, max_iter, s,
+                            QTileOps{d, P, d->st, quant_tile(d, rule), max_iter, lam32, s, ctr, rule, ms});
 }
 
 }  // namespace
@@ -2274,44 +2278,20 @@ int ldpc_phys_decode_q(const ldpc_graph *g, int32_t batch, const double *llr, in
     ldpc::QuantRule rule;
     if (int rc = quant_rule(g, flags, cn_rule, schedule, qbits, llr_scale, param_q, &rule)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (rule.tile)
-        return phys_decode_qtile(g, batch, llr, max_iter, flags, z_out, conv_out, status_out, iters_out, post_out, s,
-                                 rule);
     const DevGraph &G = g->dg;
-    const size_t n = (size_t)G.n, B = (size_t)batch;
-    auto launch = [&](const double *in, uint8_t *z, int *conv, int *status, int *iters, int16_t *post) {
-        return ldpc::launch_phys_quant(G, in, nullptr, batch, max_iter, z, conv, status, iters, post, nullptr, nullptr,
-                                       phys_quant_max_grid(), s, rule);
-    };
-    if (flags & LDPC_F_DEVICE_PTRS) {
-        HIP_TRY(launch(llr, z_out, conv_out, status_out, iters_out, post_out));
-        return LDPC_OK;
-    }
-    double *d_llr = nullptr;
-    uint8_t *d_z = nullptr;
-    int *d_i = nullptr;
-    int16_t *d_post = nullptr;
-    int rc = dev_alloc(&d_llr, B * n);
-    if (!rc) rc = dev_alloc(&d_z, B * n);
-    if (!rc) rc = dev_alloc(&d_i, 3 * B);
-    if (!rc && post_out) rc = dev_alloc(&d_post, B * n);
-    hipError_t e = hipSuccess;
-    if (!rc) {
-        e = hipMemcpyAsync(d_llr, llr, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
-        if (!e) e = launch(d_llr, d_z, d_i, d_i + B, d_i + 2 * B, d_post);
-        if (!e && z_out) e = hipMemcpyAsync(z_out, d_z, B * n, hipMemcpyDeviceToHost, s);
-        if (!e && conv_out) e = hipMemcpyAsync(conv_out, d_i, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (!e && status_out) e = hipMemcpyAsync(status_out, d_i + B, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (!e && iters_out) e = hipMemcpyAsync(iters_out, d_i + 2 * B, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (!e && post_out) e = hipMemcpyAsync(post_out, d_post, sizeof(int16_t) * B * n, hipMemcpyDeviceToHost, s);
-        if (!e) e = hipStreamSynchronize(s);
-        if (e) rc = ldpc_fail(LDPC_EDEVICE, "%s: %s", fn, hipGetErrorString(e));
-    }
-    (void)hipFree(d_llr);
-    (void)hipFree(d_z);
-    (void)hipFree(d_i);
-    (void)hipFree(d_post);
-    return rc;
+    if (rule.tile)  // int16 posteriors
+        return phys_decode_chunks(
+            g, batch, llr, flags, z_out, conv_out, status_out, iters_out, post_out, s,
+            [&](ldpc_decoder *d) { return phys_qtile_decode(d, G, max_iter, nullptr, s, nullptr, rule); },
+            [&](ldpc_decoder *d, uint8_t *z, int16_t *post) {
+                return ldpc::launch_phys_qtile_out(G, d->st, quant_tile(d, rule), z, post, s);
+            });
+    return phys_decode_staged(
+        fn, G, batch, llr, flags, z_out, {conv_out, status_out, iters_out}, post_out, s,
+        [&](const double *in, uint8_t *z, int *const *iv, int16_t *post) {
+            return ldpc::launch_phys_quant(G, in, nullptr, batch, max_iter, z, iv[0], iv[1], iv[2], post, nullptr,
+                                           nullptr, phys_quant_max_grid(), s, rule);
+        });
 }
 
 int ldpc_phys_mc_run_q(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int32_t n_points, const double *sigmas,
@@ -2319,78 +2299,27 @@ int ldpc_phys_mc_run_q(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int
                        int32_t schedule, int32_t qbits, float llr_scale, int32_t param_q, int64_t *counters_out,
                        void *stream) {
     const char *fn = "ldpc_phys_mc_run_q";
-    if (!gp) return ldpc_fail(LDPC_EINVAL, "%s: NULL graph", fn);
-    if (!d || n_points <= 0 || !sigmas || frames_per_point < 0 || frame0 < 0 || max_iter < 1 || !counters_out)
-        return ldpc_fail(LDPC_EINVAL, "%s: bad arguments", fn);
-    const DevGraph &G = d->g->dg;
-    const DevGraph &P = gp->dg;
-    if (!G.std_form && !(G.ira && d->g == gp))
-        return ldpc_fail(LDPC_EINVAL,
-                         "%s: the decoder's graph must be the code's H_std = [A | I_m], or the "
-                         "IRA graph itself", fn);
-    if (P.n != G.n || P.k != G.k)
-        return ldpc_fail(LDPC_EINVAL, "%s: physical graph shape %dx%d != %dx%d", fn, P.m, P.n, G.m, G.n);
-    for (int p = 0; p < n_points; ++p)
-        if (!(sigmas[p] > 0.0)) return ldpc_fail(LDPC_EINVAL, "%s: sigma[%d] <= 0", fn, p);
+    if (int rc = phys_mc_check(fn, d, gp, n_points, sigmas, frames_per_point, frame0, max_iter, counters_out))
+        return rc;
     if (int rc = quant_check(fn, gp, flags, cn_rule, schedule, qbits, llr_scale, param_q)) return rc;
-    if (int rc = channel_frames_check(fn, d, 0)) return rc;
+    const DevGraph &P = gp->dg;
     DeviceGuard dg(d->g->device);
     ldpc::QuantRule rule;
     if (int rc = quant_rule(gp, flags, cn_rule, schedule, qbits, llr_scale, param_q, &rule)) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (rule.tile)
         if (int rc = ensure_phys_tile(d, P)) return rc;
-    if (int rc = ensure_pbits(d, G)) return rc;
-    ldpc::RateMatchDev rm;
-    if (int rc = rate_match_dev(d, s, &rm)) return rc;
-    ldpc::HarqDev hq;
-    if (int rc = harq_dev(d, s, &hq)) return rc;
-    const int need = n_points * LDPC_MC_NCOUNT;
-    if (d->counters_cap < need) {
-        (void)hipFree(d->counters);
-        d->counters = nullptr;
-        d->counters_cap = 0;
-        if (int rc = dev_alloc(&d->counters, (size_t)need + 1)) return rc;
-        d->counters_cap = need;
-    }
-    HIP_TRY(hipMemsetAsync(d->counters, 0, sizeof(unsigned long long) * need, s));
-    if (int rc = mc_stats_begin(d, n_points, max_iter, rule.tile, s)) return rc;
-    const int64_t cap = (int64_t)d->cap_tiles * kTile;
-    for (int p = 0; p < n_points; ++p) {
-        unsigned long long *ctr = d->counters + (size_t)p * LDPC_MC_NCOUNT;
-        for (int64_t start = 0; start < frames_per_point; start += cap) {
-            const int cnt = (int)std::min<int64_t>(cap, frames_per_point - start);
-            state_bind(d, (cnt + kTile - 1) / kTile, cnt);
-            const DevState st = d->st;
-            ldpc::McStats ms;
-            mc_stats_point(d, p, frame0 + start, &ms);
-            // frames as fp32 Lambda: tiles (pLam) for the HBM tile decoder, rows for the LDS decoder
-            float *rows = (float *)d->llr_stage;
-            HIP_TRY(timed(d, LDPC_K_GEN, s, [&] {
-                return ldpc::launch_frames(G, st, phys_tile(d), seed, p, sigmas[p], frame0 + start,
-                                           rule.tile ? ldpc::kFramesTileLambda : ldpc::kFramesRowLambda, rows,
-                                           d->chan, s, rm, hq);
-            }));
-            if (rule.tile) {
-                if (ms.hist) HIP_TRY(ldpc::launch_mc_stats_slots(ms.slot_frame, ms.frame_base, cnt, s));
-                if (int rc = phys_qtile_decode(d, P, max_iter, d->pLam, s, ctr, rule, ms)) return rc;
-                HIP_TRY(timed(d, LDPC_K_COUNT, s, [&] {
-                    return ldpc::launch_phys_qtile_count(P, st, quant_tile(d, rule), ctr, s, ms);
-                }));
-                continue;
-            }
+    return phys_mc_drive(
+        d, seed, n_points, sigmas, frames_per_point, frame0, max_iter, counters_out, s,
+        rule.tile ? ldpc::kFramesTileLambda : ldpc::kFramesRowLambda, rule.tile,
+        [&](const DevState &st, int cnt, const float *rows, unsigned long long *ctr, const ldpc::McStats &ms) -> int {
+            if (rule.tile) return phys_qtile_decode(d, P, max_iter, d->pLam, s, ctr, rule, ms);
             HIP_TRY(timed(d, LDPC_K_PHYS, s, [&] {
                 return ldpc::launch_phys_quant(P, nullptr, rows, cnt, max_iter, nullptr, nullptr, nullptr, nullptr,
                                                nullptr, st.ubits, ctr, phys_quant_max_grid(), s, rule, ms);
             }));
-        }
-    }
-    std::vector<unsigned long long> h(need);
-    HIP_TRY(hipMemcpyAsync(h.data(), d->counters, sizeof(unsigned long long) * need, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (int i = 0; i < need; ++i) counters_out[i] = (int64_t)h[i];
-    if (d->ms_on) d->ms_state = 1;
-    return LDPC_OK;
+            return LDPC_OK;
+        });
 }
 
 // ------------------------------------------- physical mode, bit flipping
@@ -2483,104 +2412,38 @@ int ldpc_bf_decode(const ldpc_graph *g, int32_t batch, const double *llr, int32_
     if (k == kBfNone) return bf_no_fit(fn, G);
     DeviceGuard dg(g->device);
     hipStream_t s = (hipStream_t)stream;
-    const size_t n = (size_t)G.n, B = (size_t)batch;
-    auto launch = [&](const double *in, uint8_t *z, int *conv, int *status, int *iters, int *synw) {
-        return bf_launch(G, k, in, nullptr, 0, batch, max_iter, z, conv, status, iters, synw, nullptr, nullptr, s,
-                         weight, theta);
-    };
-    if (flags & LDPC_F_DEVICE_PTRS) {
-        HIP_TRY(launch(llr, z_out, conv_out, status_out, iters_out, synw_out));
-        return LDPC_OK;
-    }
-    double *d_llr = nullptr;
-    uint8_t *d_z = nullptr;
-    int *d_i = nullptr;
-    int rc = dev_alloc(&d_llr, B * n);
-    if (!rc) rc = dev_alloc(&d_z, B * n);
-    if (!rc) rc = dev_alloc(&d_i, 4 * B);
-    hipError_t e = hipSuccess;
-    if (!rc) {
-        e = hipMemcpyAsync(d_llr, llr, sizeof(double) * B * n, hipMemcpyHostToDevice, s);
-        if (!e) e = launch(d_llr, d_z, d_i, d_i + B, d_i + 2 * B, d_i + 3 * B);
-        if (!e && z_out) e = hipMemcpyAsync(z_out, d_z, B * n, hipMemcpyDeviceToHost, s);
-        if (!e && conv_out) e = hipMemcpyAsync(conv_out, d_i, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (!e && status_out) e = hipMemcpyAsync(status_out, d_i + B, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (!e && iters_out) e = hipMemcpyAsync(iters_out, d_i + 2 * B, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (!e && synw_out) e = hipMemcpyAsync(synw_out, d_i + 3 * B, sizeof(int) * B, hipMemcpyDeviceToHost, s);
-        if (!e) e = hipStreamSynchronize(s);
-        if (e) rc = ldpc_fail(LDPC_EDEVICE, "%s: %s", fn, hipGetErrorString(e));
-    }
-    (void)hipFree(d_llr);
-    (void)hipFree(d_z);
-    (void)hipFree(d_i);
-    return rc;
+    // bit flipping has no posterior: a fourth integer per frame, the syndrome weight
+    return phys_decode_staged(
+        fn, G, batch, llr, flags, z_out, {conv_out, status_out, iters_out, synw_out}, (float *)nullptr, s,
+        [&](const double *in, uint8_t *z, int *const *iv, float *) {
+            return bf_launch(G, k, in, nullptr, 0, batch, max_iter, z, iv[0], iv[1], iv[2], iv[3], nullptr, nullptr, s,
+                             weight, theta);
+        });
 }
 
 int ldpc_bf_mc_run(ldpc_decoder *d, const ldpc_graph *gp, uint64_t seed, int32_t n_points, const double *sigmas,
                    int64_t frames_per_point, int64_t frame0, int32_t max_iter, uint32_t flags, float weight,
                    float theta, int64_t *counters_out, void *stream) {
     const char *fn = "ldpc_bf_mc_run";
-    if (!gp) return ldpc_fail(LDPC_EINVAL, "%s: NULL graph", fn);
-    if (!d || n_points <= 0 || !sigmas || frames_per_point < 0 || frame0 < 0 || max_iter < 1 || !counters_out)
-        return ldpc_fail(LDPC_EINVAL, "%s: bad arguments", fn);
+    if (int rc = phys_mc_check(fn, d, gp, n_points, sigmas, frames_per_point, frame0, max_iter, counters_out))
+        return rc;
     if (int rc = bf_check(fn, flags, LDPC_F_BF_GENERIC, weight, theta)) return rc;
-    const DevGraph &G = d->g->dg;
     const DevGraph &P = gp->dg;
-    if (!G.std_form && !(G.ira && d->g == gp))
-        return ldpc_fail(LDPC_EINVAL,
-                         "%s: the decoder's graph must be the code's H_std = [A | I_m], or the "
-                         "IRA graph itself", fn);
-    if (P.n != G.n || P.k != G.k)
-        return ldpc_fail(LDPC_EINVAL, "%s: physical graph shape %dx%d != %dx%d", fn, P.m, P.n, G.m, G.n);
-    for (int p = 0; p < n_points; ++p)
-        if (!(sigmas[p] > 0.0)) return ldpc_fail(LDPC_EINVAL, "%s: sigma[%d] <= 0", fn, p);
-    if (int rc = channel_frames_check(fn, d, 0)) return rc;
     // the statistics are the per-frame kernel's
     const BfKernel k = bf_kernel(P, flags, weight, d->ms_on);
     if (k == kBfNone) return bf_no_fit(fn, P);
     DeviceGuard dg(d->g->device);
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = ensure_pbits(d, G)) return rc;
-    ldpc::RateMatchDev rm;
-    if (int rc = rate_match_dev(d, s, &rm)) return rc;
-    ldpc::HarqDev hq;
-    if (int rc = harq_dev(d, s, &hq)) return rc;
-    const int need = n_points * LDPC_MC_NCOUNT;
-    if (d->counters_cap < need) {
-        (void)hipFree(d->counters);
-        d->counters = nullptr;
-        d->counters_cap = 0;
-        if (int rc = dev_alloc(&d->counters, (size_t)need + 1)) return rc;
-        d->counters_cap = need;
-    }
-    HIP_TRY(hipMemsetAsync(d->counters, 0, sizeof(unsigned long long) * need, s));
-    if (int rc = mc_stats_begin(d, n_points, max_iter, false, s)) return rc;
-    const int64_t cap = (int64_t)d->cap_tiles * kTile;
-    for (int p = 0; p < n_points; ++p) {
-        unsigned long long *ctr = d->counters + (size_t)p * LDPC_MC_NCOUNT;
-        for (int64_t start = 0; start < frames_per_point; start += cap) {
-            const int cnt = (int)std::min<int64_t>(cap, frames_per_point - start);
-            state_bind(d, (cnt + kTile - 1) / kTile, cnt);
-            const DevState st = d->st;
-            ldpc::McStats ms;
-            mc_stats_point(d, p, frame0 + start, &ms);
-            float *rows = (float *)d->llr_stage;  // the frames as fp32 Lambda rows, as ldpc_phys_mc_run's LDS path
-            HIP_TRY(timed(d, LDPC_K_GEN, s, [&] {
-                return ldpc::launch_frames(G, st, phys_tile(d), seed, p, sigmas[p], frame0 + start,
-                                           ldpc::kFramesRowLambda, rows, d->chan, s, rm, hq);
-            }));
+    // the frames as fp32 Lambda rows, as ldpc_phys_mc_run's LDS path
+    return phys_mc_drive(
+        d, seed, n_points, sigmas, frames_per_point, frame0, max_iter, counters_out, s, ldpc::kFramesRowLambda, false,
+        [&](const DevState &st, int cnt, const float *rows, unsigned long long *ctr, const ldpc::McStats &ms) -> int {
             HIP_TRY(timed(d, LDPC_K_PHYS, s, [&] {
                 return bf_launch(P, k, nullptr, rows, 2, cnt, max_iter, nullptr, nullptr, nullptr, nullptr, nullptr,
                                  st.ubits, ctr, s, weight, theta, ms);
             }));
-        }
-    }
-    std::vector<unsigned long long> h(need);
-    HIP_TRY(hipMemcpyAsync(h.data(), d->counters, sizeof(unsigned long long) * need, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (int i = 0; i < need; ++i) counters_out[i] = (int64_t)h[i];
-    if (d->ms_on) d->ms_state = 1;
-    return LDPC_OK;
+            return LDPC_OK;
+        });
 }
 
 // ------------------------------------------------------- channel models

@@ -359,8 +359,13 @@ __device__ __forceinline__ bool sub_p1(const SubCtx<Q> &c, int r, const SubChunk
 // Returns whether a table value of this lane's live frame has |t| <= 1e-10
 // (sub_p1's rare-row predicate; a NaN LLR too): the column form of iteration 0
 // (sub_pass0_cols) has no rare rows and leaves such a sub-tile to the row loop.
+// The columns below `kl` (the A columns, or 0: none) are staged in the S region
+// of LDS as well, [col][F], for phase A of the column form: every lane of a
+// lane group writes its element, a frame-less lane 1.0, so all kl x F are
+// initialised.  A caller that then takes the row loop zeroes S again.
 template <int Q>
-__device__ __forceinline__ bool sub_tanh_table(const SubCtx<Q> &c, int n, int me, int nthr) {
+__device__ __forceinline__ bool sub_tanh_table(const SubCtx<Q> &c, int n, int me, int nthr, int kl) {
+    constexpr int F = SubCfg<Q>::F;
     bool tiny = false;
     for (int col = me; col < n; col += nthr) {
         const double d = *sub_c(c, col) * 0.5;
@@ -368,6 +373,7 @@ __device__ __forceinline__ bool sub_tanh_table(const SubCtx<Q> &c, int n, int me
         np_tanh_n<1, LdsTanh, true>(th, c.ttab);
         tiny |= !(fabs(th[0]) > kTiny);
         if (c.live) *sub_l(c, col) = th[0];
+        if (col < kl) c.S[(size_t)col * F] = c.live ? th[0] : 1.0;
     }
     return tiny && c.live;
 }
@@ -762,6 +768,19 @@ __device__ __forceinline__ void sub_body(SubCtx<Q> &c, int r, int m, double (&tc
 //      col_idx and multiplies the gathered table values in order; P_r goes to
 //      LDS as [m][F] in the S region (unused until pass 1: the caller checks
 //      m <= k).  A frame-less lane's P is 1.0.
+//      With `lds` (bit 3 of fp; LDPC_PASS0_LDS=0 switches it off) the A
+//      columns' factors come from LDS: sub_tanh_table has staged T[col][f],
+//      col < k, in the S region (k x F doubles: all of it), which ends the
+//      gather of 8 B per edge and frame from L (the same 147 KB about 575
+//      times over for wimax_2304_0.5; L2 served most of it).  The row's last
+//      factor, its identity column's, is gathered from L once per row; the
+//      multiplies and their order are the same.  P_r cannot go to S while the
+//      table is there: it is stored in the row's identity-edge slot of E (CSR
+//      position row_ptr[r+1] - 1, private to the row; frame-less lanes at
+//      kSubOOB), the workgroup meets at a barrier (release / acquire around
+//      it), each lane reads its products back and places them in S as above,
+//      and a second barrier starts phase B, which is unchanged and overwrites
+//      the slot with E0(r, k + r) when it reaches the identity columns.
 //   B  lane = (column, frame), 64 columns per step, the A columns and then the
 //      identity columns: each lane walks its column's CSC list (rows
 //      ascending, DevGraph::csc_*), forms E0 from P_r (LDS) and its own T,
@@ -783,7 +802,7 @@ __device__ __forceinline__ int sub_group_max(int v) {  // max over the lane grou
 }
 template <int Q>
 __device__ __forceinline__ void sub_pass0_cols(const SubCtx<Q> &c, const DevGraph &g, double *S0, uint32_t *zb,
-                                               int nllr, int me, int nthr, int &my_cnt, bool &pd) {
+                                               int nllr, int me, int nthr, bool lds, int &my_cnt, bool &pd) {
     static_assert(Q == 4, "lane groups of 16");
     constexpr int F = SubCfg<Q>::F;
     // Edges per step of a lane: phase A's gathers in flight, phase B's index loads.  Larger steps measured
@@ -807,16 +826,46 @@ __device__ __forceinline__ void sub_pass0_cols(const SubCtx<Q> &c, const DevGrap
         int cn[UA];
 #pragma unroll
         for (int u = 0; u < UA; ++u) cn[u] = sub_col(c, min(beg + u, last));
-        for (int i = 0; i < nmax; i += UA) {
-            double t[UA];
+        if (lds) {
+            // the row's last factor, its identity column's, is not staged: one gather from L per row
+            const double tI = ld_l2((const double *)(c.Lu + sub_off(c, sub_col(c, last))));
+            for (int i = 0; i < nmax; i += UA) {
+                double t[UA];
 #pragma unroll
-            for (int u = 0; u < UA; ++u) t[u] = ld_l2((const double *)(c.Lu + sub_off(c, cn[u])));
+                for (int u = 0; u < UA; ++u) t[u] = c.S[(size_t)min(cn[u], c.k - 1) * F];
 #pragma unroll
-            for (int u = 0; u < UA; ++u) cn[u] = sub_col(c, min(beg + i + UA + u, last));  // the next step's
+                for (int u = 0; u < UA; ++u) {
+                    t[u] = cn[u] < c.k ? t[u] : tI;
+                    cn[u] = sub_col(c, min(beg + i + UA + u, last));  // the next step's
+                }
 #pragma unroll
-            for (int u = 0; u < UA; ++u) P = P * ((i + u < deg && c.live) ? t[u] : 1.0);
+                for (int u = 0; u < UA; ++u) P = P * ((i + u < deg && c.live) ? t[u] : 1.0);
+            }
+            // held in the row's identity-edge slot of E (its last CSR position: private to the row, and
+            // phase B writes E0(r, k + r) there after everything else) while the table occupies S
+            st_sub_msg(c.rE, (row < m && c.live) ? ((uint32_t)last << 9) + c.lo8 : kSubOOB, P);
+        } else {
+            for (int i = 0; i < nmax; i += UA) {
+                double t[UA];
+#pragma unroll
+                for (int u = 0; u < UA; ++u) t[u] = ld_l2((const double *)(c.Lu + sub_off(c, cn[u])));
+#pragma unroll
+                for (int u = 0; u < UA; ++u) cn[u] = sub_col(c, min(beg + i + UA + u, last));  // the next step's
+#pragma unroll
+                for (int u = 0; u < UA; ++u) P = P * ((i + u < deg && c.live) ? t[u] : 1.0);
+            }
+            if (row < m) c.S[(size_t)row * F] = P;
         }
-        if (row < m) c.S[(size_t)row * F] = P;
+    }
+    if (lds) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        __syncthreads();  // the staged table is dead: every row product formed and on its way to E
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        for (int row = me; row < m; row += nthr) {
+            const uint32_t last = (uint32_t)c.row_ptr[row + 1] - 1u;
+            const double P = ld_sub_msg(c.rE, c.live ? (last << 9) + c.lo8 : kSubOOB);
+            c.S[(size_t)row * F] = c.live ? P : 1.0;  // a frame-less lane held nothing
+        }
     }
     __syncthreads();  // every P_r in LDS, every gather of the table done
     // B: columns
@@ -880,8 +929,8 @@ __device__ __forceinline__ void sub_pass0_cols(const SubCtx<Q> &c, const DevGrap
             if (c.live) *sub_l(c, col) = Lj;
         }
     }
-    // the last barrier above: every P_r read
-    for (int i = threadIdx.x; i < m * F; i += blockDim.x) S0[i] = 0.0;
+    // the last barrier above: every P_r read (with `lds`, S held k x F table values: m <= k)
+    for (int i = threadIdx.x; i < (lds ? c.k : m) * F; i += blockDim.x) S0[i] = 0.0;
 }
 
 // Fixed-point exit (fp != 0; LDPC_FIXED_POINT=0 switches it off).  A pass is a
@@ -1034,13 +1083,20 @@ __global__ __launch_bounds__(64 * kSW, 1) void tile_sub_kernel(DevGraph g, DevSt
     // iteration 0 runs column by column (sub_pass0_cols): bit 2 of fp, P_r fits the S region, and no live
     // frame's table value is tiny (the vote below, in the control word that pass 0 rewrites)
     bool cols0 = (fp & 4) != 0 && m <= g.k;
+    // ... and its phase A gathers the A columns' table values from LDS (bit 3 of fp, LDPC_PASS0_LDS):
+    // staged only where the column form can still follow
+    const bool lds0 = cols0 && (fp & 8) != 0;
     fp &= 3;  // the exit's bits
     if (max_iter > 0) {  // iteration 0's tanh table, in L (sub_tanh_table); the other wavefronts gather it with ld_l2
         c.live = livel[f] != 0;
-        if (sub_tanh_table<Q>(c, g.n, me, nthr)) lds_st(flags + 2 * kSR + 1, 1);
+        if (sub_tanh_table<Q>(c, g.n, me, nthr, lds0 ? g.k : 0)) lds_st(flags + 2 * kSR + 1, 1);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         __syncthreads();
         cols0 = cols0 && uniform(flags[2 * kSR + 1]) == 0;
+        if (lds0 && !cols0) {  // the vote is lost: the row loop sums into S
+            for (int i = threadIdx.x; i < g.k * F; i += blockDim.x) S[i] = 0.0;
+            __syncthreads();
+        }
     }
     int it0 = 0;
     if (max_iter > 0 && cols0) {
@@ -1051,7 +1107,7 @@ __global__ __launch_bounds__(64 * kSW, 1) void tile_sub_kernel(DevGraph g, DevSt
         // scratch in the normal passes' P1 (profiles/r10_pass0_cols).
         int my_cnt = 0;
         bool pd = false;
-        sub_pass0_cols<Q>(c, g, S, zb, nllr, me, nthr, my_cnt, pd);
+        sub_pass0_cols<Q>(c, g, S, zb, nllr, me, nthr, lds0, my_cnt, pd);
         if (nllr && my_cnt) atomicAdd(cntl + f, my_cnt);
         if (fp && pd && c.live) atomicOr((uint32_t *)pdiffl + f, 1u);
         __syncthreads();
@@ -1496,8 +1552,11 @@ hipError_t launch_tile_sub(const DevGraph &g, const DevState &st, int max_iter, 
     const char *e = getenv("LDPC_FIXED_POINT");
     const char *en = getenv("LDPC_FP_NEXT");
     // LDPC_PASS0_COLS=0 (bit 2 of fp, no part of the exit): iteration 0 by the row loop, not column by column
+    // LDPC_PASS0_LDS=0 (bit 3 of fp, neither): the column form's row products gather the table from L, not from LDS
     const char *ec = getenv("LDPC_PASS0_COLS");
-    const int fp = ((!e || atoi(e) != 0) ? (1 | ((!en || atoi(en) != 0) ? 2 : 0)) : 0) | ((!ec || atoi(ec) != 0) ? 4 : 0);
+    const char *el = getenv("LDPC_PASS0_LDS");
+    const int fp = ((!e || atoi(e) != 0) ? (1 | ((!en || atoi(en) != 0) ? 2 : 0)) : 0) | ((!ec || atoi(ec) != 0) ? 4 : 0) |
+                   ((!el || atoi(el) != 0) ? 8 : 0);
     tile_sub_kernel<4><<<st.ntiles * 4, 64 * kSW, lds, s>>>(g, st, max_iter, nllr ? 1 : 0, g.col_idx, g.row_ptr,
                                                             kAtanhCoef, fp);
     return hipGetLastError();

@@ -1722,13 +1722,13 @@ void mc_stats_point(const ldpc_decoder *d, int p, int64_t frame_base, ldpc::McSt
 }
 
 // Decode the frames bound in d->st with HBM-resident tile kernels, a family's
-// own behind `ops` (PhysTileOps, QTileOps): up to max_iter sweeps, then what
+// own behind `ops` (TileOps: PhysTileOps, QTileOps): up to max_iter sweeps, then what
 // the family needs to finish.  The host reads the running-tile and
 // running-frame counts after sweep(it) for it < 4 and every 4th iteration
 // after, and stops issuing sweeps once they are zero.  With ops.ctr (a
 // Monte-Carlo run: only the counters leave the device) the running frames are
 // compacted into the first tiles once at most a quarter of the launched slots
-// hold them, the finished frames counted into ctr first (phys_tile.hip), and
+// hold them, the finished frames counted into ctr first (phys_tile_state.hip), and
 // the rest at the end.  ops.st is the family's copy of d->st: its ntiles
 // shrinks with each compaction.
 template <class Ops>
@@ -1748,7 +1748,7 @@ int phys_tile_sweeps(ldpc_decoder *d, int max_iter, hipStream_t s, Ops &&ops) {
             // where frames stop after 20-40 iterations (the -2.5 dB
             // waterfall: -1.4 % with it at every poll of it < 4,
             // profiles/r5_ab/r5ao_ab)
-            if (ops.has_early_exit && (it == 1 || it == 2))
+            if (!ops.layered() && (it == 1 || it == 2))
                 HIP_TRY(timed(d, LDPC_K_PHYS_VN, s, [&] { return ops.early_exit(it); }));
             int running[2] = {0, 0};  // tiles, frames
             HIP_TRY(hipMemcpyAsync(&running[0], d->pactive + it, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -1774,63 +1774,85 @@ int phys_tile_sweeps(ldpc_decoder *d, int max_iter, hipStream_t s, Ops &&ops) {
     return LDPC_OK;
 }
 
-// phys_tile_sweeps on the fp32 tile kernels (phys_tile.hip), channel LLRs in
-// d->ch (from_ch) or the generator's Lambda tiles.  Flooding: a CN and a VN
-// sweep per iteration, then a syndrome-only sweep and final().  Layered: per
-// iteration one launch per layer, in order on the stream, then the syndrome of
-// b = (L < 0) and the exits -- on the device every iteration, so the results
-// never depend on the polls; the exit of iteration max_iter - 1 stops the
-// frames still running (no final sweep).
-struct PhysTileOps {
+// What phys_tile_sweeps runs, once for both families: the layers of an
+// iteration, a sweep with its two timed brackets, and the bookkeeping of
+// phys_tile_state.hip -- early exit, count, compaction, the end.  Self (CRTP)
+// adds what differs: `t` (a PhysTile / QTile: E, L, Lam, bad, cap), `rule`
+// (layer_ptr set: layered), init(), layer(it, lbeg, lrows), cn(it), vn(it) and
+// the flooding syndromes early_syn(it) -> bad[(it+1)&1] and last_syn() ->
+// bad[max_iter&1].  Layered: per iteration one launch per layer, in order on
+// the stream, then the syndrome of b = (L < 0) and the exits -- on the device
+// every iteration, so the results never depend on the polls; the exit of
+// iteration max_iter - 1 stops the frames still running (no final sweep).
+template <class Self>
+struct TileOps {
     ldpc_decoder *d;
     const DevGraph &P;
     DevState st;
-    PhysTile pt;
     int max_iter;
-    bool from_ch;
     hipStream_t s;
     unsigned long long *ctr;
-    const PhysRule &rule;
     const ldpc::McStats &ms;
-    const bool has_early_exit = !rule.layer_ptr;  // flooding only
 
-    hipError_t init() { return ldpc::launch_phys_tile_init(P, st, pt, from_ch, s); }
+    Self &self() { return static_cast<Self &>(*this); }
+    bool layered() { return self().rule.layer_ptr != nullptr; }
     hipError_t layers(int it) {
+        const auto &rule = self().rule;
         for (int l = 0; l < rule.n_layers; ++l) {
             const int lbeg = rule.h_layer_ptr[l], lrows = rule.h_layer_ptr[l + 1] - lbeg;
-            if (hipError_t e = ldpc::launch_phys_layer_tile(P, st, pt, it, lbeg, lrows, s, rule)) return e;
+            if (hipError_t e = self().layer(it, lbeg, lrows)) return e;
         }
         return hipSuccess;
     }
     hipError_t sweep(int it) {
-        if (hipError_t e = timed(d, LDPC_K_PHYS_CN, s, [&] {
-                return rule.layer_ptr ? layers(it) : ldpc::launch_phys_tile_cn(P, st, pt, it, false, s, rule);
-            }))
+        const auto &t = self().t;
+        if (hipError_t e = timed(d, LDPC_K_PHYS_CN, s, [&] { return layered() ? layers(it) : self().cn(it); }))
             return e;
         return timed(d, LDPC_K_PHYS_VN, s, [&] {
-            return rule.layer_ptr ? ldpc::launch_phys_layer_exit(P, st, pt, it, d->pactive, max_iter, s)
-                                  : ldpc::launch_phys_tile_vn(P, st, pt, it, d->pactive, max_iter, s);
+            return layered() ? ldpc::launch_phys_layer_exit(P, st, t.L, t.bad, t.cap, it, d->pactive, max_iter, s)
+                             : self().vn(it);
         });
     }
-    hipError_t early_exit(int it) {
-        return ldpc::launch_phys_tile_early_exit(P, st, pt, it, d->pactive, max_iter, s);
+    hipError_t early_exit(int it) {  // flooding only
+        if (hipError_t e = self().early_syn(it)) return e;
+        return ldpc::launch_phys_tile_exit(st, self().t.bad, self().t.cap, it, d->pactive, max_iter, s);
     }
-    hipError_t count() { return ldpc::launch_phys_tile_count(P, st, pt, ctr, s, ms); }
+    hipError_t count() { return ldpc::launch_phys_tile_count(P, st, self().t.L, ctr, s, ms); }
     hipError_t compact(int nt) {
-        return ldpc::launch_phys_compact(P, st, pt, nt, d->cap_tiles * kTile, d->cpairs, s,
+        const auto &t = self().t;
+        return ldpc::launch_phys_compact(P, st, t.E, t.L, t.Lam, t.bad, nt, d->cap_tiles * kTile, d->cpairs, s,
                                          ms.hist ? ms.slot_frame : nullptr);
     }
-    hipError_t finish() {
-        if (rule.layer_ptr) return hipSuccess;
-        if (hipError_t e = ldpc::launch_phys_tile_cn(P, st, pt, max_iter, true, s, rule)) return e;
-        return ldpc::launch_phys_tile_final(P, st, pt, max_iter, s);
+    hipError_t finish() {  // flooding: the frames that converge on the last iteration
+        if (layered()) return hipSuccess;
+        if (hipError_t e = self().last_syn()) return e;
+        return ldpc::launch_phys_tile_final(st, self().t.bad, self().t.cap, max_iter, s);
     }
+};
+
+// The fp32 tile kernels (phys_tile.hip), channel LLRs in d->ch (from_ch) or
+// the generator's Lambda tiles.  Flooding: a CN and a VN sweep per iteration;
+// the early syndrome comes from the VN sweep's hard-decision bytes, the last
+// one from a syndrome-only CN sweep.
+struct PhysTileOps : TileOps<PhysTileOps> {
+    PhysTile t;
+    bool from_ch;
+    const PhysRule &rule;
+
+    hipError_t init() { return ldpc::launch_phys_tile_init(P, st, t, from_ch, s); }
+    hipError_t layer(int it, int lbeg, int lrows) {
+        return ldpc::launch_phys_layer_tile(P, st, t, it, lbeg, lrows, s, rule);
+    }
+    hipError_t cn(int it) { return ldpc::launch_phys_tile_cn(P, st, t, it, false, s, rule); }
+    hipError_t vn(int it) { return ldpc::launch_phys_tile_vn(P, st, t, it, d->pactive, max_iter, s); }
+    hipError_t early_syn(int it) { return ldpc::launch_phys_tile_syn(P, st, t, it, s); }
+    hipError_t last_syn() { return ldpc::launch_phys_tile_cn(P, st, t, max_iter, true, s, rule); }
 };
 
 int phys_tile_decode(ldpc_decoder *d, const DevGraph &P, int max_iter, bool from_ch, hipStream_t s,
                      unsigned long long *ctr, const PhysRule &rule, const ldpc::McStats &ms = ldpc::McStats{}) {
     return phys_tile_sweeps(d, max_iter, s,
-                            PhysTileOps{d, P, d->st, phys_tile(d), max_iter, from_ch, s, ctr, rule, ms});
+                            PhysTileOps{{d, P, d->st, max_iter, s, ctr, ms}, phys_tile(d), from_ch, rule});
 }
 
 // Whether a rule phys_rule filled runs one LDS kernel on graph P, not the HBM tile kernels.
@@ -1913,7 +1935,7 @@ int phys_decode_any(const char *fn, const ldpc_graph *g, int32_t batch, const do
         g, batch, llr, flags, z_out, conv_out, status_out, iters_out, post_out, s,
         [&](ldpc_decoder *d) { return phys_tile_decode(d, G, max_iter, true, s, nullptr, rule); },
         [&](ldpc_decoder *d, uint8_t *z, float *post) {
-            return ldpc::launch_phys_tile_out(G, d->st, phys_tile(d), z, post, s);
+            return ldpc::launch_phys_tile_out(G, d->st, phys_tile(d).L, z, post, s);
         });
 }
 
@@ -2179,7 +2201,7 @@ ldpc::QTile quant_tile(ldpc_decoder *d, const ldpc::QuantRule &rule) {
     ldpc::QTile qt{};
     qt.E = reinterpret_cast<int8_t *>(d->pE);
     qt.L = reinterpret_cast<int16_t *>(d->pL);
-    qt.Lam = reinterpret_cast<int8_t *>(d->pL) + 2 * cap * n;
+    qt.Lam = rule.layer_ptr ? nullptr : reinterpret_cast<int8_t *>(d->pL) + 2 * cap * n;  // flooding only
     qt.bad = d->pbad;
     qt.cap = (int)cap;
     qt.qmax = (1 << (rule.qbits - 1)) - 1;
@@ -2189,61 +2211,29 @@ ldpc::QTile quant_tile(ldpc_decoder *d, const ldpc::QuantRule &rule) {
     return qt;
 }
 
-// phys_tile_sweeps on the fixed-point tile kernels (phys_qtile.hip); lam32:
-// the generator's fp32 Lambda tiles, or null: the channel LLRs in d->ch.
-// Sweeps and exits as PhysTileOps for either schedule; flooding ends with
-// final() alone (the frames that converge on the last iteration; the layered
-// exit stops every frame itself).
-struct QTileOps {
-    ldpc_decoder *d;
-    const DevGraph &P;
-    DevState st;
-    ldpc::QTile qt;
-    int max_iter;
+// TileOps on the fixed-point tile kernels (phys_qtile.hip); lam32: the
+// generator's fp32 Lambda tiles, or null: the channel LLRs in d->ch.  Both
+// flooding syndromes are read from L16.
+struct QTileOps : TileOps<QTileOps> {
+    ldpc::QTile t;
     const float *lam32;
-    hipStream_t s;
-    unsigned long long *ctr;
     const ldpc::QuantRule &rule;
-    const ldpc::McStats &ms;
-    const bool has_early_exit = !rule.layer_ptr;  // flooding only
 
-    hipError_t init() { return ldpc::launch_phys_qtile_init(P, st, qt, lam32, !rule.layer_ptr, s); }
-    hipError_t layers(int it) {
-        for (int l = 0; l < rule.n_layers; ++l) {
-            const int lbeg = rule.h_layer_ptr[l], lrows = rule.h_layer_ptr[l + 1] - lbeg;
-            if (hipError_t e = ldpc::launch_phys_qlayer_tile(P, st, qt, rule.cn, it, lbeg, lrows, rule.layer_rows, s))
-                return e;
-        }
-        return hipSuccess;
+    hipError_t init() { return ldpc::launch_phys_qtile_init(P, st, t, lam32, !rule.layer_ptr, s); }
+    hipError_t layer(int it, int lbeg, int lrows) {
+        return ldpc::launch_phys_qlayer_tile(P, st, t, rule.cn, it, lbeg, lrows, rule.layer_rows, s);
     }
-    hipError_t sweep(int it) {
-        if (hipError_t e = timed(d, LDPC_K_PHYS_CN, s, [&] {
-                return rule.layer_ptr ? layers(it) : ldpc::launch_phys_qtile_cn(P, st, qt, rule.cn, it, s);
-            }))
-            return e;
-        return timed(d, LDPC_K_PHYS_VN, s, [&] {
-            return rule.layer_ptr ? ldpc::launch_phys_qlayer_exit(P, st, qt, it, d->pactive, max_iter, s)
-                                  : ldpc::launch_phys_qtile_vn(P, st, qt, it, d->pactive, max_iter, s);
-        });
-    }
-    hipError_t early_exit(int it) {
-        return ldpc::launch_phys_qtile_early_exit(P, st, qt, it, d->pactive, max_iter, s);
-    }
-    hipError_t count() { return ldpc::launch_phys_qtile_count(P, st, qt, ctr, s, ms); }
-    hipError_t compact(int nt) {
-        return ldpc::launch_phys_qtile_compact(P, st, qt, !rule.layer_ptr, nt, d->cap_tiles * kTile, d->cpairs, s,
-                                               ms.hist ? ms.slot_frame : nullptr);
-    }
-    hipError_t finish() {
-        return rule.layer_ptr ? hipSuccess : ldpc::launch_phys_qtile_final(P, st, qt, max_iter, s);
-    }
+    hipError_t cn(int it) { return ldpc::launch_phys_qtile_cn(P, st, t, rule.cn, it, s); }
+    hipError_t vn(int it) { return ldpc::launch_phys_qtile_vn(P, st, t, it, d->pactive, max_iter, s); }
+    hipError_t early_syn(int it) { return ldpc::launch_phys_tile_lsyn(P, st, t.L, t.bad, t.cap, (it + 1) & 1, s); }
+    hipError_t last_syn() { return ldpc::launch_phys_tile_lsyn(P, st, t.L, t.bad, t.cap, max_iter & 1, s); }
 };
 
 int phys_qtile_decode(ldpc_decoder *d, const DevGraph &P, int max_iter, const float *lam32, hipStream_t s,
                       unsigned long long *ctr, const ldpc::QuantRule &rule,
                       const ldpc::McStats &ms = ldpc::McStats{}) {
     return phys_tile_sweeps(d, max_iter, s,
-                            QTileOps{d, P, d->st, quant_tile(d, rule), max_iter, lam32, s, ctr, rule, ms});
+                            QTileOps{{d, P, d->st, max_iter, s, ctr, ms}, quant_tile(d, rule), lam32, rule});
 }
 
 }  // namespace
@@ -2284,7 +2274,7 @@ int ldpc_phys_decode_q(const ldpc_graph *g, int32_t batch, const double *llr, in
             g, batch, llr, flags, z_out, conv_out, status_out, iters_out, post_out, s,
             [&](ldpc_decoder *d) { return phys_qtile_decode(d, G, max_iter, nullptr, s, nullptr, rule); },
             [&](ldpc_decoder *d, uint8_t *z, int16_t *post) {
-                return ldpc::launch_phys_qtile_out(G, d->st, quant_tile(d, rule), z, post, s);
+                return ldpc::launch_phys_tile_out(G, d->st, quant_tile(d, rule).L, z, post, s);
             });
     return phys_decode_staged(
         fn, G, batch, llr, flags, z_out, {conv_out, status_out, iters_out}, post_out, s,

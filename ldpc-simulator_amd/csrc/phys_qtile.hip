@@ -11,6 +11,8 @@
 // so a wavefront's message access is 64 B contiguous and a posterior access
 // 128 B; DevState's done / conv / status / iters / tile_active, the bad flags,
 // xcd_item placement and the host's poll-and-compact loop are phys_tile.hip's.
+// This file keeps the load and the sweeps; the exits, the syndrome, out, count
+// and the compaction are phys_tile_state.hip's, shared with the fp32 family.
 // There is no padded table and no 16-bit column index here: any n.
 //
 //   phys_qlayer_tile  one launch per layer and iteration (stream order is the
@@ -24,9 +26,10 @@
 //   phys_qvn_tile     L = clamp(Lam + sum E, +-Pmax), an int32 sum clamped
 //                     once (1 B per edge + 3 B per column); a frame whose
 //                     syndrome was zero stops, converged at it - 1.
-//   phys_qsyn_tile    row parities of b = (L < 0) read from L16 itself: the
-//                     layered exit of every iteration, the flooding early exit
-//                     (iterations 1 and 2) and the sweep after the last one.
+//   phys_lsyn_tile    (phys_tile_state.hip) row parities of b = (L < 0) read
+//                     from L16 itself: the layered exit of every iteration, the
+//                     flooding early exit (iterations 1 and 2) and the sweep
+//                     after the last one.
 // Iteration 0 takes E = 0 from `first` and every edge of a running frame is
 // written once per sweep, so E needs no memset.  Only the lanes of running
 // frames load or store: a stopped frame's L16 is its posterior, and the lanes
@@ -88,12 +91,7 @@ __global__ void phys_qtile_init_kernel(DevGraph g, DevState st, QTile qt, const 
     if (i < (size_t)st.ntiles * kTile) {
         const int f = (int)i;
         const bool valid = f < st.count;
-        st.done[f] = valid ? 0 : 2;  // 2: no frame (never counted)
-        st.conv[f] = -1;
-        st.status[f] = 1;
-        st.iters[f] = 0;
-        qt.bad[f] = 0;
-        qt.bad[qt.cap + f] = 0;
+        frame_reset(st, qt.bad, qt.cap, f, valid);
         if ((f & 63) == 0) st.tile_active[f >> 6] = valid ? 1 : 0;
     }
 }
@@ -356,241 +354,25 @@ __global__ __launch_bounds__(256) void phys_qvn_tile_kernel(DevGraph g, DevState
     }
 }
 
-// ------------------------------------------------- syndrome and the exits
-// Row parities of b = (L < 0) of the running frames, read from L16, one
-// wavefront per (tile, kRowsPerWave rows) -> bad[slot][frame].
-__global__ __launch_bounds__(256) void phys_qsyn_tile_kernel(DevGraph g, DevState st, QTile qt, int slot,
-                                                             int per_tile, int items,
-                                                             const int *__restrict__ row_ptr,
-                                                             const int *__restrict__ col_idx) {
-    const int lane = threadIdx.x & 63;
-    const int wave = uniform(threadIdx.x >> 6);
-    for (int item = blockIdx.x; item < items; item += gridDim.x) {
-        int tile, part;
-        xcd_item(item, per_tile, tile, part);
-        if (tile >= st.ntiles || !st.tile_active[tile]) continue;
-        const int f = tile * kTile + lane;
-        const bool live = st.done[f] == 0;
-        if (__ballot(live) == 0ull) continue;
-        const int16_t *Lt = qt.L + (size_t)tile * g.n * kTile + lane;
-        uint32_t bad = 0u;
-        const int r0 = (part * 4 + wave) * kRowsPerWave;
-        for (int rr = 0; rr < kRowsPerWave; ++rr) {
-            const int r = r0 + rr;
-            if (r >= g.m) break;
-            uint32_t lx = 0u;
-            if (live)
-                for (int e = row_ptr[r]; e < row_ptr[r + 1]; ++e) lx ^= (uint32_t)(int)Lt[col_idx[e] * kTile];
-            bad |= lx >> 31;
-        }
-        if (live && bad) qt.bad[slot * qt.cap + f] = 1;
-    }
-}
-
-// flooding, after phys_qsyn_tile into bad[(it+1)&1]: the frames whose flag
-// stayed 0 stop, converged at it (phys_tile_exit)
-__global__ __launch_bounds__(64) void phys_qtile_exit_kernel(DevState st, QTile qt, int it, int *active_count,
-                                                             int max_iter) {
-    const int tile = blockIdx.x;
-    const int lane = threadIdx.x;
-    const int f = tile * kTile + lane;
-    const bool live = st.tile_active[tile] && st.done[f] == 0;
-    const bool conv_now = live && qt.bad[((it + 1) & 1) * qt.cap + f] == 0;
-    if (conv_now) {
-        st.done[f] = 1;
-        st.conv[f] = it;
-        st.status[f] = 0;
-        st.iters[f] = it + 1;
-    }
-    const unsigned long long still = __ballot(live && !conv_now);
-    if (lane == 0) {
-        if (st.tile_active[tile]) st.tile_active[tile] = still != 0ull ? 1 : 0;
-        if (still) {
-            atomicAdd(&active_count[it], 1);
-            atomicAdd(&active_count[max_iter + it], (int)__popcll(still));
-        }
-    }
-}
-
-// flooding, after the syndrome of the last iteration's posterior (phys_tile_final)
-__global__ void phys_qtile_final_kernel(DevState st, QTile qt, int max_iter) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= st.ntiles * kTile || st.done[f]) return;
-    const bool ok = qt.bad[(max_iter & 1) * qt.cap + f] == 0;
-    st.done[f] = 1;
-    st.conv[f] = ok ? max_iter - 1 : -1;
-    st.status[f] = ok ? 0 : 1;
-    st.iters[f] = max_iter;
-}
-
-// layered, after phys_qsyn_tile into bad[0]: the exit of iteration it (phys_layer_exit)
-__global__ __launch_bounds__(64) void phys_qlayer_exit_kernel(DevState st, QTile qt, int it, int *active_count,
-                                                              int max_iter) {
-    const int tile = blockIdx.x;
-    const int lane = threadIdx.x;
-    const int f = tile * kTile + lane;
-    const bool active = st.tile_active[tile] != 0;
-    const bool live = active && st.done[f] == 0;
-    const bool conv_now = live && qt.bad[f] == 0;
-    qt.bad[f] = 0;  // for the next iteration's syndrome
-    const bool last = it + 1 >= max_iter;
-    if (conv_now) {
-        st.done[f] = 1;
-        st.conv[f] = it;
-        st.status[f] = 0;
-        st.iters[f] = it + 1;
-    } else if (live && last) {
-        st.done[f] = 1;
-        st.conv[f] = -1;
-        st.status[f] = 1;
-        st.iters[f] = max_iter;
-    }
-    const unsigned long long still = __ballot(live && !conv_now && !last);
-    if (lane == 0) {
-        if (active) st.tile_active[tile] = still != 0ull ? 1 : 0;
-        if (still) {
-            atomicAdd(&active_count[it], 1);
-            atomicAdd(&active_count[max_iter + it], (int)__popcll(still));
-        }
-    }
-}
-
-// ------------------------------------------------------------ companions
-// L16 tiles -> row-major z = (L < 0 ? 0 : 1) and the integer posteriors
-__global__ void phys_qtile_out_kernel(DevGraph g, DevState st, QTile qt, uint8_t *z, int16_t *post) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)st.count * g.n) return;
-    const int f = (int)(i / g.n);
-    const int j = (int)(i % g.n);
-    const int16_t L = qt.L[((size_t)(f >> 6) * g.n + j) * kTile + (f & 63)];
-    if (z) z[i] = L < 0 ? 0 : 1;
-    if (post) post[i] = L;
-}
-
-// main.py counters; block = one wavefront x (tile, 1024 info columns) (phys_tile_count)
-__global__ __launch_bounds__(64) void phys_qtile_count_kernel(DevGraph g, DevState st, QTile qt,
-                                                              unsigned long long *ctr, McStats ms) {
-    const int kw = (g.k + 31) >> 5;
-    const int per_tile = (g.k + 1023) >> 10 > 0 ? (g.k + 1023) >> 10 : 1;
-    const int tile = blockIdx.x / per_tile, part = blockIdx.x % per_tile;
-    const int lane = threadIdx.x;
-    const int f = tile * kTile + lane;
-    const bool valid = st.done[f] == 1;  // finished and not counted yet
-    const bool failed = valid && st.status[f] != 0;
-    unsigned long long err = 0;
-    if (ms.hist ? valid : failed) {  // BER counts failed frames only; the statistics need the converged ones too
-        const uint32_t *Ut = st.ubits + (size_t)tile * kw * kTile + lane;
-        const int16_t *Lt = qt.L + (size_t)tile * g.n * kTile + lane;
-        const int j1 = min(g.k, (part + 1) * 1024);
-        for (int j = part * 1024; j < j1; ++j) {
-            const uint32_t u = (Ut[(j >> 5) * kTile] >> (j & 31)) & 1u;
-            err += (u != (Lt[j * kTile] < 0 ? 1u : 0u)) ? 1 : 0;
-        }
-    }
-    const unsigned long long e = wave_sum(failed ? err : 0ull);
-    if (lane == 0 && e) atomicAdd(&ctr[2], e);
-    if (ms.hist) mc_stats_tile(ms, st, tile, per_tile, lane, valid, failed, (int)err);
-    if (part != 0) return;
-    const int cv = valid ? st.conv[f] : -1;
-    unsigned long long v[7] = {valid ? 1ull : 0ull, failed ? 1ull : 0ull, 0, cv >= 0 ? (unsigned long long)cv : 0,
-                               cv >= 0 ? 1ull : 0ull, 0, valid ? (unsigned long long)st.iters[f] : 0};
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-        if (i == 2 || i == 5) continue;
-        const unsigned long long s = wave_sum(v[i]);
-        if (lane == 0 && s) atomicAdd(&ctr[i], s);
-    }
-}
-
-// Compaction (phys_tile.hip's, on the integer arrays): the finished frames
-// were counted; mark them, plan, move each running frame's lanes of E8, L16,
-// Lam8 (flooding) and the u bits, reset the destination's per-frame state.
-__global__ void phys_qmark_counted_kernel(DevState st) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f < st.ntiles * kTile && st.done[f] == 1) st.done[f] = 2;
-}
-__global__ void phys_qcompact_move_kernel(DevGraph g, DevState st, QTile qt, int flooding, int cap,
-                                          const int *pairs) {
-    const int P = pairs[0];
-    const int kw = (g.k + 31) >> 5;
-    const int64_t nlam = flooding ? g.n : 0;
-    const int64_t items = (int64_t)g.nnz + g.n + nlam + kw;
-    const int64_t total = (int64_t)P * items;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int p = (int)(i % P);  // pair-fastest: neighbouring lanes of one item
-        int64_t it = i / P;
-        const int src = pairs[1 + p], dst = pairs[1 + cap + p];
-        const size_t sT = src >> 6, sl = src & 63, dT = dst >> 6, dl = dst & 63;
-        if (it < g.nnz) {
-            qt.E[(dT * g.nnz + it) * kTile + dl] = qt.E[(sT * g.nnz + it) * kTile + sl];
-            continue;
-        }
-        it -= g.nnz;
-        if (it < g.n) {
-            qt.L[(dT * g.n + it) * kTile + dl] = qt.L[(sT * g.n + it) * kTile + sl];
-            continue;
-        }
-        it -= g.n;
-        if (it < nlam) {
-            qt.Lam[(dT * g.n + it) * kTile + dl] = qt.Lam[(sT * g.n + it) * kTile + sl];
-            continue;
-        }
-        it -= nlam;
-        st.ubits[(dT * kw + it) * kTile + dl] = st.ubits[(sT * kw + it) * kTile + sl];
-    }
-}
-__global__ void phys_qcompact_flags_kernel(DevState st, QTile qt, int cap, const int *pairs,
-                                           long long *slot_frame) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= pairs[0]) return;
-    const int src = pairs[1 + p], dst = pairs[1 + cap + p];
-    if (slot_frame) slot_frame[dst] = slot_frame[src];  // the frame's global index moves with it
-    st.done[dst] = 0;
-    st.conv[dst] = -1;
-    st.status[dst] = 1;
-    st.iters[dst] = 0;
-    qt.bad[dst] = 0;
-    qt.bad[qt.cap + dst] = 0;
-    st.tile_active[dst >> 6] = 1;
-    st.done[src] = 2;  // moved: nothing to count here
-}
-
-int rows_per_tile(int rows) { return (rows + 4 * kRowsPerWave - 1) / (4 * kRowsPerWave); }
-
 template <int CN>
 void launch_qlayer_rule(const DevGraph &g, const DevState &st, const QTile &qt, int it, int lbeg, int lrows,
                         const int *layer_rows, hipStream_t s) {
     const int per_tile = rows_per_tile(lrows);
     const int items = (int)xcd_items(st.ntiles, per_tile);
-    const unsigned grid = stride_grid(items);
-    if (g.max_row_deg <= 8)
-        phys_qlayer_tile_kernel<8, CN><<<grid, 256, 0, s>>>(g, st, qt, it, lbeg, lrows, per_tile, items, g.row_ptr,
-                                                            g.col_idx, layer_rows);
-    else if (g.max_row_deg <= 16)
-        phys_qlayer_tile_kernel<16, CN><<<grid, 256, 0, s>>>(g, st, qt, it, lbeg, lrows, per_tile, items, g.row_ptr,
-                                                             g.col_idx, layer_rows);
-    else
-        phys_qlayer_tile_kernel<32, CN><<<grid, 256, 0, s>>>(g, st, qt, it, lbeg, lrows, per_tile, items, g.row_ptr,
-                                                             g.col_idx, layer_rows);
+    for_row_deg(g.max_row_deg, [&](auto deg) {
+        phys_qlayer_tile_kernel<decltype(deg)::value, CN><<<stride_grid(items), 256, 0, s>>>(
+            g, st, qt, it, lbeg, lrows, per_tile, items, g.row_ptr, g.col_idx, layer_rows);
+    });
 }
 
 template <int CN>
 void launch_qcn_rule(const DevGraph &g, const DevState &st, const QTile &qt, int it, hipStream_t s) {
     const int per_tile = rows_per_tile(g.m);
     const int items = (int)xcd_items(st.ntiles, per_tile);
-    const unsigned grid = stride_grid(items);
-    if (g.max_row_deg <= 8)
-        phys_qcn_tile_kernel<8, CN><<<grid, 256, 0, s>>>(g, st, qt, it, per_tile, items, g.row_ptr, g.col_idx);
-    else if (g.max_row_deg <= 16)
-        phys_qcn_tile_kernel<16, CN><<<grid, 256, 0, s>>>(g, st, qt, it, per_tile, items, g.row_ptr, g.col_idx);
-    else
-        phys_qcn_tile_kernel<32, CN><<<grid, 256, 0, s>>>(g, st, qt, it, per_tile, items, g.row_ptr, g.col_idx);
-}
-
-void launch_qsyn(const DevGraph &g, const DevState &st, const QTile &qt, int slot, hipStream_t s) {
-    const int per_tile = rows_per_tile(g.m);
-    const int items = (int)xcd_items(st.ntiles, per_tile);
-    phys_qsyn_tile_kernel<<<stride_grid(items), 256, 0, s>>>(g, st, qt, slot, per_tile, items, g.row_ptr, g.col_idx);
+    for_row_deg(g.max_row_deg, [&](auto deg) {
+        phys_qcn_tile_kernel<decltype(deg)::value, CN><<<stride_grid(items), 256, 0, s>>>(
+            g, st, qt, it, per_tile, items, g.row_ptr, g.col_idx);
+    });
 }
 
 }  // namespace
@@ -612,14 +394,6 @@ hipError_t launch_phys_qlayer_tile(const DevGraph &g, const DevState &st, const 
     case kCnOms: launch_qlayer_rule<kCnOms>(g, st, qt, it, lbeg, lrows, layer_rows, s); break;
     default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
-}
-
-hipError_t launch_phys_qlayer_exit(const DevGraph &g, const DevState &st, const QTile &qt, int it, int *active_count,
-                                   int max_iter, hipStream_t s) {
-    if (st.ntiles <= 0) return hipSuccess;
-    launch_qsyn(g, st, qt, 0, s);
-    phys_qlayer_exit_kernel<<<st.ntiles, kTile, 0, s>>>(st, qt, it, active_count, max_iter);
     return hipGetLastError();
 }
 
@@ -645,48 +419,6 @@ hipError_t launch_phys_qtile_vn(const DevGraph &g, const DevState &st, const QTi
     else
         phys_qvn_tile_kernel<0><<<stride_grid(items), 256, 0, s>>>(g, st, qt, it, per_tile, items, g.csc_ptr,
                                                                    g.csc_edge, active_count, max_iter);
-    return hipGetLastError();
-}
-
-hipError_t launch_phys_qtile_early_exit(const DevGraph &g, const DevState &st, const QTile &qt, int it,
-                                        int *active_count, int max_iter, hipStream_t s) {
-    if (st.ntiles <= 0) return hipSuccess;
-    launch_qsyn(g, st, qt, (it + 1) & 1, s);
-    if (hipError_t e = hipMemsetAsync(active_count + it, 0, sizeof(int), s)) return e;
-    if (hipError_t e = hipMemsetAsync(active_count + max_iter + it, 0, sizeof(int), s)) return e;
-    phys_qtile_exit_kernel<<<st.ntiles, kTile, 0, s>>>(st, qt, it, active_count, max_iter);
-    return hipGetLastError();
-}
-
-hipError_t launch_phys_qtile_final(const DevGraph &g, const DevState &st, const QTile &qt, int max_iter,
-                                   hipStream_t s) {
-    if (st.ntiles <= 0) return hipSuccess;
-    launch_qsyn(g, st, qt, max_iter & 1, s);
-    phys_qtile_final_kernel<<<grid_for((size_t)st.ntiles * kTile, 256), 256, 0, s>>>(st, qt, max_iter);
-    return hipGetLastError();
-}
-
-hipError_t launch_phys_qtile_out(const DevGraph &g, const DevState &st, const QTile &qt, uint8_t *z, int16_t *post,
-                                 hipStream_t s) {
-    const size_t total = (size_t)st.count * g.n;
-    if (total && (z || post)) phys_qtile_out_kernel<<<grid_for(total, 256), 256, 0, s>>>(g, st, qt, z, post);
-    return hipGetLastError();
-}
-
-hipError_t launch_phys_qtile_count(const DevGraph &g, const DevState &st, const QTile &qt, unsigned long long *ctr,
-                                   hipStream_t s, const McStats &ms) {
-    if (st.ntiles <= 0) return hipSuccess;
-    const int per_tile = std::max(1, (g.k + 1023) >> 10);
-    phys_qtile_count_kernel<<<st.ntiles * per_tile, 64, 0, s>>>(g, st, qt, ctr, ms);
-    return hipGetLastError();
-}
-
-hipError_t launch_phys_qtile_compact(const DevGraph &g, const DevState &st, const QTile &qt, bool flooding, int nt,
-                                     int cap, int *pairs, hipStream_t s, long long *slot_frame) {
-    phys_qmark_counted_kernel<<<grid_for((size_t)st.ntiles * kTile, 256), 256, 0, s>>>(st);
-    if (hipError_t e = launch_compact_plan(st, nt, cap, pairs, s)) return e;
-    phys_qcompact_move_kernel<<<2048, 256, 0, s>>>(g, st, qt, flooding ? 1 : 0, cap, pairs);
-    phys_qcompact_flags_kernel<<<grid_for((size_t)cap, 256), 256, 0, s>>>(st, qt, cap, pairs, slot_frame);
     return hipGetLastError();
 }
 

@@ -20,16 +20,19 @@
 //                 the previous iteration (exactly the LDS kernel's exit).
 // After the last iteration a syndrome-only CN sweep and phys_tile_final give
 // the frames that converge on it.
+// The bookkeeping around the sweeps -- the exits, phys_tile_final, the
+// syndrome read from L, out, count and the compaction -- is shared with the
+// fixed-point family and lives in phys_tile_state.hip; this file keeps the
+// load, the sweeps and the early syndrome from the VN sweep's bytes.
 // Monte-Carlo runs (counters only) compact: once at most a quarter of the
 // launched slots still run, the finished frames are counted and the running
 // ones move into the first tiles (phys_compact_*), so the last sweeps launch
 // those tiles only -- at 1 dB on the DVB-S2 profile the fourth CN sweep ran
 // for ~5 % of the frames, scattered over every tile, at the cost of a full
-// sweep (profiles/r5s_c5).  done[]: 0 running, 1 finished (to be counted),
-// 2 counted, moved away, or no frame.  Each (tile, row block) and (tile, column
-// block) is placed XCD-aware like cn_kernel.
+// sweep (profiles/r5s_c5).  Each (tile, row block) and (tile, column block) is
+// placed XCD-aware like cn_kernel.
 // The layered min-sum schedule runs on the same tiles (phys_layer_tile: one
-// launch per layer, then a syndrome sweep and the exit; further down).
+// launch per layer, then phys_tile_state.hip's syndrome and exit; further down).
 // Frames come from frame_kernels.hip (directly as fp32 Lambda/L for IRA
 // codes, else as fp64 ch converted by phys_tile_init).
 #include <hip/hip_runtime.h>
@@ -62,12 +65,7 @@ __global__ void phys_tile_init_kernel(DevGraph g, DevState st, PhysTile pt, int 
     if (i < (size_t)st.ntiles * kTile) {
         const int f = (int)i;
         const bool valid = f < st.count;
-        st.done[f] = valid ? 0 : 2;  // 2: no frame (never counted)
-        st.conv[f] = -1;
-        st.status[f] = 1;
-        st.iters[f] = 0;
-        pt.bad[f] = 0;
-        pt.bad[pt.cap + f] = 0;
+        frame_reset(st, pt.bad, pt.cap, f, valid);
         if ((f & 63) == 0) st.tile_active[f >> 6] = valid ? 1 : 0;
     }
 }
@@ -345,148 +343,6 @@ __global__ __launch_bounds__(256) void phys_tile_syn_kernel(DevGraph g, DevState
         if (live && bad) pt.bad[((it + 1) & 1) * pt.cap + f] = 1;
     }
 }
-__global__ __launch_bounds__(64) void phys_tile_exit_kernel(DevState st, PhysTile pt, int it, int *active_count,
-                                                            int max_iter) {
-    const int tile = blockIdx.x;
-    const int lane = threadIdx.x;
-    const int f = tile * kTile + lane;
-    const bool live = st.tile_active[tile] && st.done[f] == 0;
-    const bool conv_now = live && pt.bad[((it + 1) & 1) * pt.cap + f] == 0;
-    if (conv_now) {  // the syndrome of iteration it is zero
-        st.done[f] = 1;
-        st.conv[f] = it;
-        st.status[f] = 0;
-        st.iters[f] = it + 1;
-    }
-    const unsigned long long still = __ballot(live && !conv_now);
-    if (lane == 0) {
-        if (st.tile_active[tile]) st.tile_active[tile] = still != 0ull ? 1 : 0;
-        if (still) {
-            atomicAdd(&active_count[it], 1);
-            atomicAdd(&active_count[max_iter + it], (int)__popcll(still));
-        }
-    }
-}
-
-// after the syndrome-only sweep of "iteration" max_iter
-__global__ void phys_tile_final_kernel(DevState st, PhysTile pt, int max_iter) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= st.ntiles * kTile || st.done[f]) return;
-    const bool ok = pt.bad[(max_iter & 1) * pt.cap + f] == 0;
-    st.done[f] = 1;
-    st.conv[f] = ok ? max_iter - 1 : -1;
-    st.status[f] = ok ? 0 : 1;
-    st.iters[f] = max_iter;
-}
-
-// L32 tiles -> row-major z = (L < 0 ? 0 : 1) (bit estimate ^ 1) and post
-__global__ void phys_tile_out_kernel(DevGraph g, DevState st, PhysTile pt, uint8_t *z, float *post) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)st.count * g.n) return;
-    const int f = (int)(i / g.n);
-    const int j = (int)(i % g.n);
-    const float L = pt.L[((size_t)(f >> 6) * g.n + j) * kTile + (f & 63)];
-    if (z) z[i] = L < 0.0f ? 0 : 1;
-    if (post) post[i] = L;
-}
-
-// main.py counters; block = one wavefront x (tile, 1024 info columns)
-__global__ __launch_bounds__(64) void phys_tile_count_kernel(DevGraph g, DevState st, PhysTile pt,
-                                                             unsigned long long *ctr, McStats ms) {
-    const int kw = (g.k + 31) >> 5;
-    const int per_tile = (g.k + 1023) >> 10 > 0 ? (g.k + 1023) >> 10 : 1;
-    const int tile = blockIdx.x / per_tile, part = blockIdx.x % per_tile;
-    const int lane = threadIdx.x;
-    const int f = tile * kTile + lane;
-    const bool valid = st.done[f] == 1;  // finished and not counted yet (phys_tile_init, phys_compact)
-    const bool failed = valid && st.status[f] != 0;
-    unsigned long long err = 0;
-    // BER counts failed frames only (main.py:130-138); the statistics need the converged ones too
-    const bool cmp = ms.hist ? valid : failed;
-    if (__ballot(cmp) != 0ull) {
-        const uint32_t *Ut = st.ubits + (size_t)tile * kw * kTile + lane;
-        const float *Lt = pt.L + (size_t)tile * g.n * kTile + lane;
-        const int j1 = min(g.k, (part + 1) * 1024);
-        for (int j = part * 1024; j < j1; ++j) {
-            const uint32_t u = (Ut[(j >> 5) * kTile] >> (j & 31)) & 1u;
-            err += (u != (Lt[j * kTile] < 0.0f ? 1u : 0u)) ? 1 : 0;
-        }
-        if (!cmp) err = 0;
-    }
-    const unsigned long long e = wave_sum(failed ? err : 0ull);
-    if (lane == 0 && e) atomicAdd(&ctr[2], e);
-    if (ms.hist) mc_stats_tile(ms, st, tile, per_tile, lane, valid, failed, (int)err);
-    if (part != 0) return;
-    const int cv = valid ? st.conv[f] : -1;
-    unsigned long long v[7] = {valid ? 1ull : 0ull, failed ? 1ull : 0ull, 0, cv >= 0 ? (unsigned long long)cv : 0,
-                               cv >= 0 ? 1ull : 0ull, 0, valid ? (unsigned long long)st.iters[f] : 0};
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-        if (i == 2 || i == 5) continue;
-        const unsigned long long s = wave_sum(v[i]);
-        if (lane == 0 && s) atomicAdd(&ctr[i], s);
-    }
-}
-
-// McStats::slot_frame of a fresh chunk
-__global__ void mc_stats_slots_kernel(long long *slot_frame, long long base, int count) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f < count) slot_frame[f] = base + f;
-}
-
-// Compaction (Monte-Carlo runs): after the finished frames were counted,
-// mark them counted; then move each running frame of the plan (spa_kernels
-// compact plan: sources = running slots in tiles >= nt, destinations =
-// finished slots below) -- its lanes of E32, L32, Lambda and the u bits --
-// and reset the destination's per-frame state.  Sources and destinations are
-// disjoint, so the moves need no ordering.
-__global__ void phys_mark_counted_kernel(DevState st) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f < st.ntiles * kTile && st.done[f] == 1) st.done[f] = 2;
-}
-__global__ void phys_compact_move_kernel(DevGraph g, DevState st, PhysTile pt, int cap, const int *pairs) {
-    const int P = pairs[0];
-    const int kw = (g.k + 31) >> 5;
-    const int64_t items = (int64_t)g.nnz + 2 * (int64_t)g.n + kw;
-    const int64_t total = (int64_t)P * items;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int p = (int)(i % P);  // pair-fastest: neighbouring lanes of one item
-        int64_t it = i / P;
-        const int src = pairs[1 + p], dst = pairs[1 + cap + p];
-        const size_t sT = src >> 6, sl = src & 63, dT = dst >> 6, dl = dst & 63;
-        if (it < g.nnz) {
-            pt.E[(dT * g.nnz + it) * kTile + dl] = pt.E[(sT * g.nnz + it) * kTile + sl];
-            continue;
-        }
-        it -= g.nnz;
-        if (it < g.n) {
-            pt.L[(dT * g.n + it) * kTile + dl] = pt.L[(sT * g.n + it) * kTile + sl];
-            continue;
-        }
-        it -= g.n;
-        if (it < g.n) {
-            pt.Lam[(dT * g.n + it) * kTile + dl] = pt.Lam[(sT * g.n + it) * kTile + sl];
-            continue;
-        }
-        it -= g.n;
-        st.ubits[(dT * kw + it) * kTile + dl] = st.ubits[(sT * kw + it) * kTile + sl];
-    }
-}
-__global__ void phys_compact_flags_kernel(DevState st, PhysTile pt, int cap, const int *pairs,
-                                          long long *slot_frame) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= pairs[0]) return;
-    const int src = pairs[1 + p], dst = pairs[1 + cap + p];
-    if (slot_frame) slot_frame[dst] = slot_frame[src];  // the frame's global index moves with it
-    st.done[dst] = 0;
-    st.conv[dst] = -1;
-    st.status[dst] = 1;
-    st.iters[dst] = 0;
-    pt.bad[dst] = 0;
-    pt.bad[pt.cap + dst] = 0;
-    st.tile_active[dst >> 6] = 1;
-    st.done[src] = 2;  // moved: nothing to count here
-}
 
 // ------------------------------------------- layered min-sum on the tiles
 // The layered schedule (phys_layered.hip's arithmetic, operation for
@@ -584,71 +440,6 @@ __global__ __launch_bounds__(256) void phys_layer_tile_kernel(DevGraph g, DevSta
     }
 }
 
-// After the last layer of an iteration: the row parities of b = (L < 0) of the
-// running frames, one wavefront per (tile, 4 rows) as phys_tile_syn, read
-// from L itself -> bad[frame] (one slot: phys_layer_exit consumes and clears it).
-__global__ __launch_bounds__(256) void phys_layer_syn_kernel(DevGraph g, DevState st, PhysTile pt, int per_tile,
-                                                             int items, const int *__restrict__ row_ptr,
-                                                             const int *__restrict__ col_idx) {
-    const int lane = threadIdx.x & 63;
-    const int wave = uniform(threadIdx.x >> 6);
-    for (int item = blockIdx.x; item < items; item += gridDim.x) {
-        int tile, part;
-        xcd_item(item, per_tile, tile, part);
-        if (tile >= st.ntiles || !st.tile_active[tile]) continue;
-        const int f = tile * kTile + lane;
-        const bool live = st.done[f] == 0;
-        if (__ballot(live) == 0ull) continue;
-        const float *Lt = pt.L + (size_t)tile * g.n * kTile + lane;
-        uint32_t bad = 0u;
-        const int r0 = (part * 4 + wave) * kRowsPerWave;
-        for (int rr = 0; rr < kRowsPerWave; ++rr) {
-            const int r = r0 + rr;
-            if (r >= g.m) break;
-            uint32_t hp = 0u;
-            if (live)
-                for (int e = row_ptr[r]; e < row_ptr[r + 1]; ++e) hp ^= Lt[col_idx[e] * kTile] < 0.0f ? 1u : 0u;
-            bad |= hp;
-        }
-        if (live && bad) pt.bad[f] = 1;
-    }
-}
-
-// The exit of iteration it: a running frame with no bad row stops, converged
-// at it (phys_tile_exit); after the last iteration the frames still running
-// stop unconverged (phys_tile_final).  Runs every iteration, so the results
-// never depend on when the host polls the running counts.
-__global__ __launch_bounds__(64) void phys_layer_exit_kernel(DevState st, PhysTile pt, int it, int *active_count,
-                                                             int max_iter) {
-    const int tile = blockIdx.x;
-    const int lane = threadIdx.x;
-    const int f = tile * kTile + lane;
-    const bool active = st.tile_active[tile] != 0;
-    const bool live = active && st.done[f] == 0;
-    const bool conv_now = live && pt.bad[f] == 0;
-    pt.bad[f] = 0;  // for the next iteration's syndrome
-    const bool last = it + 1 >= max_iter;
-    if (conv_now) {
-        st.done[f] = 1;
-        st.conv[f] = it;
-        st.status[f] = 0;
-        st.iters[f] = it + 1;
-    } else if (live && last) {
-        st.done[f] = 1;
-        st.conv[f] = -1;
-        st.status[f] = 1;
-        st.iters[f] = max_iter;
-    }
-    const unsigned long long still = __ballot(live && !conv_now && !last);
-    if (lane == 0) {
-        if (active) st.tile_active[tile] = still != 0ull ? 1 : 0;
-        if (still) {
-            atomicAdd(&active_count[it], 1);
-            atomicAdd(&active_count[max_iter + it], (int)__popcll(still));
-        }
-    }
-}
-
 }  // namespace
 
 hipError_t launch_phys_tile_init(const DevGraph &g, const DevState &st, const PhysTile &pt, bool convert,
@@ -664,19 +455,12 @@ namespace {
 template <int CN>
 void launch_cn_tile_rule(const DevGraph &g, const DevState &st, const PhysTile &pt, int it, bool syn_only,
                          float param, hipStream_t s) {
-    const int per_tile = (g.m + 4 * kRowsPerWave - 1) / (4 * kRowsPerWave);
+    const int per_tile = rows_per_tile(g.m);
     const int items = (int)xcd_items(st.ntiles, per_tile);
-    const unsigned grid = stride_grid(items);
-    const int so = syn_only ? 1 : 0;
-    if (g.max_row_deg <= 8)
-        phys_cn_tile_kernel<8, CN><<<grid, 256, 0, s>>>(g, st, pt, it, so, per_tile, items, g.row_ptr, g.col_idx,
-                                                        param);
-    else if (g.max_row_deg <= 16)
-        phys_cn_tile_kernel<16, CN><<<grid, 256, 0, s>>>(g, st, pt, it, so, per_tile, items, g.row_ptr, g.col_idx,
-                                                         param);
-    else
-        phys_cn_tile_kernel<32, CN><<<grid, 256, 0, s>>>(g, st, pt, it, so, per_tile, items, g.row_ptr, g.col_idx,
-                                                         param);
+    for_row_deg(g.max_row_deg, [&](auto deg) {
+        phys_cn_tile_kernel<decltype(deg)::value, CN><<<stride_grid(items), 256, 0, s>>>(
+            g, st, pt, it, syn_only ? 1 : 0, per_tile, items, g.row_ptr, g.col_idx, param);
+    });
 }
 
 }  // namespace
@@ -705,27 +489,11 @@ hipError_t launch_phys_tile_vn(const DevGraph &g, const DevState &st, const Phys
     return hipGetLastError();
 }
 
-hipError_t launch_phys_tile_final(const DevGraph &, const DevState &st, const PhysTile &pt, int max_iter,
-                                  hipStream_t s) {
-    phys_tile_final_kernel<<<grid_for((size_t)st.ntiles * kTile, 256), 256, 0, s>>>(st, pt, max_iter);
-    return hipGetLastError();
-}
-
-hipError_t launch_phys_tile_out(const DevGraph &g, const DevState &st, const PhysTile &pt, uint8_t *z, float *post,
-                                hipStream_t s) {
-    const size_t total = (size_t)st.count * g.n;
-    if (total && (z || post)) phys_tile_out_kernel<<<grid_for(total, 256), 256, 0, s>>>(g, st, pt, z, post);
-    return hipGetLastError();
-}
-
-hipError_t launch_phys_tile_early_exit(const DevGraph &g, const DevState &st, const PhysTile &pt, int it,
-                                       int *active_count, int max_iter, hipStream_t s) {
-    const int per_tile = (g.m + 4 * kRowsPerWave - 1) / (4 * kRowsPerWave);
+hipError_t launch_phys_tile_syn(const DevGraph &g, const DevState &st, const PhysTile &pt, int it, hipStream_t s) {
+    if (st.ntiles <= 0) return hipSuccess;
+    const int per_tile = rows_per_tile(g.m);
     const int items = (int)xcd_items(st.ntiles, per_tile);
     phys_tile_syn_kernel<<<stride_grid(items), 256, 0, s>>>(g, st, pt, it, per_tile, items, g.row_ptr, g.col_idx);
-    if (hipError_t e = hipMemsetAsync(active_count + it, 0, sizeof(int), s)) return e;
-    if (hipError_t e = hipMemsetAsync(active_count + max_iter + it, 0, sizeof(int), s)) return e;
-    phys_tile_exit_kernel<<<st.ntiles, kTile, 0, s>>>(st, pt, it, active_count, max_iter);
     return hipGetLastError();
 }
 
@@ -734,18 +502,12 @@ namespace {
 template <int CN>
 void launch_layer_tile_rule(const DevGraph &g, const DevState &st, const PhysTile &pt, int it, int lbeg, int lrows,
                             const PhysRule &rule, hipStream_t s) {
-    const int per_tile = (lrows + 4 * kRowsPerWave - 1) / (4 * kRowsPerWave);
+    const int per_tile = rows_per_tile(lrows);
     const int items = (int)xcd_items(st.ntiles, per_tile);
-    const unsigned grid = stride_grid(items);
-    if (g.max_row_deg <= 8)
-        phys_layer_tile_kernel<8, CN><<<grid, 256, 0, s>>>(g, st, pt, it, lbeg, lrows, per_tile, items, g.row_ptr,
-                                                           g.col_idx, rule.layer_rows, rule.param);
-    else if (g.max_row_deg <= 16)
-        phys_layer_tile_kernel<16, CN><<<grid, 256, 0, s>>>(g, st, pt, it, lbeg, lrows, per_tile, items, g.row_ptr,
-                                                            g.col_idx, rule.layer_rows, rule.param);
-    else
-        phys_layer_tile_kernel<32, CN><<<grid, 256, 0, s>>>(g, st, pt, it, lbeg, lrows, per_tile, items, g.row_ptr,
-                                                            g.col_idx, rule.layer_rows, rule.param);
+    for_row_deg(g.max_row_deg, [&](auto deg) {
+        phys_layer_tile_kernel<decltype(deg)::value, CN><<<stride_grid(items), 256, 0, s>>>(
+            g, st, pt, it, lbeg, lrows, per_tile, items, g.row_ptr, g.col_idx, rule.layer_rows, rule.param);
+    });
 }
 
 }  // namespace
@@ -759,38 +521,6 @@ hipError_t launch_phys_layer_tile(const DevGraph &g, const DevState &st, const P
     case kCnOms: launch_layer_tile_rule<kCnOms>(g, st, pt, it, lbeg, lrows, rule, s); break;
     default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
-}
-
-hipError_t launch_phys_layer_exit(const DevGraph &g, const DevState &st, const PhysTile &pt, int it,
-                                  int *active_count, int max_iter, hipStream_t s) {
-    if (st.ntiles <= 0) return hipSuccess;
-    const int per_tile = (g.m + 4 * kRowsPerWave - 1) / (4 * kRowsPerWave);
-    const int items = (int)xcd_items(st.ntiles, per_tile);
-    phys_layer_syn_kernel<<<stride_grid(items), 256, 0, s>>>(g, st, pt, per_tile, items, g.row_ptr, g.col_idx);
-    phys_layer_exit_kernel<<<st.ntiles, kTile, 0, s>>>(st, pt, it, active_count, max_iter);
-    return hipGetLastError();
-}
-
-hipError_t launch_phys_compact(const DevGraph &g, const DevState &st, const PhysTile &pt, int nt, int cap, int *pairs,
-                               hipStream_t s, long long *slot_frame) {
-    phys_mark_counted_kernel<<<grid_for((size_t)st.ntiles * kTile, 256), 256, 0, s>>>(st);
-    if (hipError_t e = launch_compact_plan(st, nt, cap, pairs, s)) return e;
-    phys_compact_move_kernel<<<2048, 256, 0, s>>>(g, st, pt, cap, pairs);
-    phys_compact_flags_kernel<<<grid_for((size_t)cap, 256), 256, 0, s>>>(st, pt, cap, pairs, slot_frame);
-    return hipGetLastError();
-}
-
-hipError_t launch_mc_stats_slots(long long *slot_frame, long long base, int count, hipStream_t s) {
-    if (!slot_frame || count <= 0) return hipSuccess;
-    mc_stats_slots_kernel<<<grid_for((size_t)count, 256), 256, 0, s>>>(slot_frame, base, count);
-    return hipGetLastError();
-}
-
-hipError_t launch_phys_tile_count(const DevGraph &g, const DevState &st, const PhysTile &pt,
-                                  unsigned long long *ctr, hipStream_t s, const McStats &ms) {
-    const int per_tile = std::max(1, (g.k + 1023) >> 10);
-    phys_tile_count_kernel<<<st.ntiles * per_tile, 64, 0, s>>>(g, st, pt, ctr, ms);
     return hipGetLastError();
 }
 

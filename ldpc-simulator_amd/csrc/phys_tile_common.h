@@ -1,12 +1,16 @@
 // phys_tile_common.h -- what the HBM tile kernels of physical mode share
 // (phys_tile.hip: fp32; phys_qtile.hip: fixed point): the work split of a
-// wavefront, the XCD-aware placement of the work items and the launch sizes.
+// wavefront, the XCD-aware placement of the work items, the launch sizes, the
+// kDeg dispatch of the row kernels and the reset of a slot's per-frame state.
+// The bookkeeping kernels of both families -- exits, final, syndrome from L,
+// out, count, compaction -- are in phys_tile_state.hip, once.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
 
 #include "spa_device.h"
 
@@ -84,9 +88,32 @@ __device__ __forceinline__ void mc_stats_tile(const McStats &ms, const DevState 
     }
 }
 
+// Slot f before its frame's first sweep (the init kernels; the destination of
+// a compaction move): running, or without a frame (done = 2: never counted).
+// The caller sets tile_active.
+__device__ __forceinline__ void frame_reset(const DevState &st, int *bad, int cap, int f, bool valid) {
+    st.done[f] = valid ? 0 : 2;
+    st.conv[f] = -1;
+    st.status[f] = 1;
+    st.iters[f] = 0;
+    bad[f] = 0;
+    bad[cap + f] = 0;
+}
+
 inline unsigned grid_for(size_t total, int block) { return (unsigned)((total + block - 1) / block); }
 inline unsigned xcd_items(int ntiles, int per_tile) { return (unsigned)(((ntiles + 7) / 8) * 8 * per_tile); }
 // 256 CUs x 16 blocks of 4 waves (a multiple of 8, see xcd_item)
 inline unsigned stride_grid(int items) { return (unsigned)std::min(items, 4096); }
+// work items of a tile in a row sweep: a block of 4 wavefronts takes 4 kRowsPerWave rows
+inline int rows_per_tile(int rows) { return (rows + 4 * kRowsPerWave - 1) / (4 * kRowsPerWave); }
+
+// f(std::integral_constant<int, kDeg>) for the row kernels' kDeg of a graph:
+// the smallest of 8 / 16 / 32 that holds max_row_deg, 32 for any longer row
+template <class F>
+void for_row_deg(int max_row_deg, F &&f) {
+    if (max_row_deg <= 8) f(std::integral_constant<int, 8>{});
+    else if (max_row_deg <= 16) f(std::integral_constant<int, 16>{});
+    else f(std::integral_constant<int, 32>{});
+}
 
 }  // namespace ldpc

@@ -187,7 +187,7 @@ hipError_t launch_refill(const DevGraph &g, const DevState &st, uint64_t seed, i
 // streaming tail: move the frames running in tiles >= nt into finished slots
 // of tiles < nt (pairs: 1 + 2 cap ints of scratch)
 hipError_t launch_compact(const DevGraph &g, const DevState &st, int nt, int cap, int *pairs, hipStream_t s);
-// the plan alone (phys_tile.hip's compaction moves its own arrays)
+// the plan alone (phys_tile_state.hip's compaction moves its own arrays)
 hipError_t launch_compact_plan(const DevState &st, int nt, int cap, int *pairs, hipStream_t s);
 hipError_t launch_finalize(const DevGraph &g, const DevState &st, uint8_t *z, double *post,
                            hipStream_t s);
@@ -371,40 +371,23 @@ hipError_t launch_phys_tile_cn(const DevGraph &g, const DevState &st, const Phys
 hipError_t launch_phys_tile_vn(const DevGraph &g, const DevState &st, const PhysTile &pt, int it, int *active_count,
                                int max_iter, hipStream_t s);  // active_count [2 max_iter]: tiles, then frames
 // Syndrome of the posterior of iteration it right after VN(it), from the VN's
-// hard-decision bytes, and the exits it implies (conv = it): the frames that
-// converge there skip CN(it+1); active_count[it] / [max_iter + it] recounted
-hipError_t launch_phys_tile_early_exit(const DevGraph &g, const DevState &st, const PhysTile &pt, int it,
-                                       int *active_count, int max_iter, hipStream_t s);
+// hard-decision bytes, into bad[(it+1)&1]: launch_phys_tile_exit then stops the
+// frames that converged there, which skip CN(it+1)
+hipError_t launch_phys_tile_syn(const DevGraph &g, const DevState &st, const PhysTile &pt, int it, hipStream_t s);
 // Layered min-sum on the tiles: the rows layer_rows[lbeg .. lbeg + lrows) of one
 // layer (rule.cn kCnNms / kCnOms, rule.layer_rows set); launches on one stream
 // are the order of the layers.
 hipError_t launch_phys_layer_tile(const DevGraph &g, const DevState &st, const PhysTile &pt, int it, int lbeg,
                                   int lrows, hipStream_t s, const PhysRule &rule);
-// After an iteration's last layer: syndrome of b = (L < 0), then the exits
-// (converged at it; unconverged after it = max_iter - 1) and the running counts
-// active_count[it], active_count[max_iter + it] (zeroed by the caller).
-hipError_t launch_phys_layer_exit(const DevGraph &g, const DevState &st, const PhysTile &pt, int it,
-                                  int *active_count, int max_iter, hipStream_t s);
-// Monte-Carlo compaction of the running frames into tiles < nt (the finished ones counted first);
-// slot_frame (McStats, or null) moves with them
-hipError_t launch_phys_compact(const DevGraph &g, const DevState &st, const PhysTile &pt, int nt, int cap, int *pairs,
-                               hipStream_t s, long long *slot_frame = nullptr);
-// McStats::slot_frame of a freshly generated chunk: slot f holds frame base + f
-hipError_t launch_mc_stats_slots(long long *slot_frame, long long base, int count, hipStream_t s);
-hipError_t launch_phys_tile_final(const DevGraph &g, const DevState &st, const PhysTile &pt, int max_iter,
-                                  hipStream_t s);
-hipError_t launch_phys_tile_out(const DevGraph &g, const DevState &st, const PhysTile &pt, uint8_t *z, float *post,
-                                hipStream_t s);
-hipError_t launch_phys_tile_count(const DevGraph &g, const DevState &st, const PhysTile &pt,
-                                  unsigned long long *ctr, hipStream_t s, const McStats &ms = McStats{});
 
 // fixed-point min-sum with the state in HBM (phys_qtile.hip): the tile layout
 // and the per-frame state (DevState, bad flags) of phys_tile.hip, the integers
-// of phys_quant.hip.  One byte per message and two per posterior.
+// of phys_quant.hip.  One byte per message and two per posterior.  The members
+// E, L, Lam, bad and cap are what the shared bookkeeping (below) takes.
 struct QTile {
     int8_t *E;     // [tile][nnz][64] check->variable messages, CSR edge order
     int16_t *L;    // [tile][n][64] posteriors (L < 0 -> bit 1)
-    int8_t *Lam;   // [tile][n][64] quantized Lambda, flooding only
+    int8_t *Lam;   // [tile][n][64] quantized Lambda, flooding only (layered: null)
     int *bad;      // [2][cap] row-syndrome flags, by iteration parity (layered: slot 0)
     int cap;       // frames of capacity (stride of bad)
     int qmax, pmax, param_q;
@@ -418,23 +401,46 @@ hipError_t launch_phys_qtile_init(const DevGraph &g, const DevState &st, const Q
 // one layer of the layered schedule (as launch_phys_layer_tile); cn kCnNms / kCnOms
 hipError_t launch_phys_qlayer_tile(const DevGraph &g, const DevState &st, const QTile &qt, int cn, int it, int lbeg,
                                    int lrows, const int *layer_rows, hipStream_t s);
-// layered: syndrome of b = (L < 0) and the exits of iteration it (as launch_phys_layer_exit)
-hipError_t launch_phys_qlayer_exit(const DevGraph &g, const DevState &st, const QTile &qt, int it, int *active_count,
-                                   int max_iter, hipStream_t s);
-// flooding: check sweep, variable sweep, the early syndrome + exits, and the last syndrome + final
+// flooding: check sweep and variable sweep
 hipError_t launch_phys_qtile_cn(const DevGraph &g, const DevState &st, const QTile &qt, int cn, int it, hipStream_t s);
 hipError_t launch_phys_qtile_vn(const DevGraph &g, const DevState &st, const QTile &qt, int it, int *active_count,
                                 int max_iter, hipStream_t s);
-hipError_t launch_phys_qtile_early_exit(const DevGraph &g, const DevState &st, const QTile &qt, int it,
-                                        int *active_count, int max_iter, hipStream_t s);
-hipError_t launch_phys_qtile_final(const DevGraph &g, const DevState &st, const QTile &qt, int max_iter,
-                                   hipStream_t s);
-hipError_t launch_phys_qtile_out(const DevGraph &g, const DevState &st, const QTile &qt, uint8_t *z, int16_t *post,
+
+// The bookkeeping both tile families share (phys_tile_state.hip): bad [2][cap]
+// and cap are PhysTile's / QTile's, E / L / Lam their arrays -- float / float /
+// float or int8_t / int16_t / int8_t, the two instances of the templates.
+// Row parities of b = (L < 0) of the running frames, read from L -> bad[slot]
+template <class TL>
+hipError_t launch_phys_tile_lsyn(const DevGraph &g, const DevState &st, const TL *L, int *bad, int cap, int slot,
                                  hipStream_t s);
-hipError_t launch_phys_qtile_count(const DevGraph &g, const DevState &st, const QTile &qt, unsigned long long *ctr,
-                                   hipStream_t s, const McStats &ms = McStats{});
-hipError_t launch_phys_qtile_compact(const DevGraph &g, const DevState &st, const QTile &qt, bool flooding, int nt,
-                                     int cap, int *pairs, hipStream_t s, long long *slot_frame = nullptr);
+// Flooding, after a syndrome into bad[(it+1)&1]: the frames whose flag stayed 0
+// stop (conv = it); active_count[it] / [max_iter + it] recounted
+hipError_t launch_phys_tile_exit(const DevState &st, int *bad, int cap, int it, int *active_count, int max_iter,
+                                 hipStream_t s);
+// Flooding, after the syndrome of the last posterior into bad[max_iter&1]: every running frame stops
+hipError_t launch_phys_tile_final(const DevState &st, int *bad, int cap, int max_iter, hipStream_t s);
+// Layered, after an iteration's last layer: syndrome of b = (L < 0) into bad[0], then the exits
+// (converged at it; unconverged after it = max_iter - 1) and the running counts
+// active_count[it], active_count[max_iter + it] (zeroed by the caller).
+template <class TL>
+hipError_t launch_phys_layer_exit(const DevGraph &g, const DevState &st, const TL *L, int *bad, int cap, int it,
+                                  int *active_count, int max_iter, hipStream_t s);
+// the tiles to row-major z = (L < 0 ? 0 : 1) and post (either may be null)
+template <class TL>
+hipError_t launch_phys_tile_out(const DevGraph &g, const DevState &st, const TL *L, uint8_t *z, TL *post,
+                                hipStream_t s);
+// main.py's counters and McStats of the frames with done == 1
+template <class TL>
+hipError_t launch_phys_tile_count(const DevGraph &g, const DevState &st, const TL *L, unsigned long long *ctr,
+                                  hipStream_t s, const McStats &ms = McStats{});
+// Monte-Carlo compaction of the running frames into tiles < nt (the finished ones counted first);
+// Lam null: no Lambda plane to move; slot_frame (McStats, or null) moves with the frames.
+// cap: the decoder's frame capacity, the stride of bad and of the plan in pairs.
+template <class TE, class TL, class TLam>
+hipError_t launch_phys_compact(const DevGraph &g, const DevState &st, TE *E, TL *L, TLam *Lam, int *bad, int nt,
+                               int cap, int *pairs, hipStream_t s, long long *slot_frame = nullptr);
+// McStats::slot_frame of a freshly generated chunk: slot f holds frame base + f
+hipError_t launch_mc_stats_slots(long long *slot_frame, long long base, int count, hipStream_t s);
 
 // --- Philox4x32-10 (Salmon et al., SC'11), shared by host tests and device ---
 __host__ __device__ inline void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {

@@ -33,6 +33,7 @@ CASES = {
     "spa_flooding_lds": ("phys_mc_run", {}, {}, False),
     "spa_flooding_hbm": ("phys_mc_run", dict(hbm=True), {}, False),
     "spa_flooding_hbm_nocompact": ("phys_mc_run", dict(hbm=True), {"LDPC_PHYS_COMPACT": "0"}, False),
+    "nms_flooding_hbm": ("phys_mc_run", dict(cn="nms", hbm=True), {}, False),
     "nms_layered_lds": ("phys_mc_run", dict(cn="nms", schedule="layered"), {}, False),
     "nms_layered_tile": ("phys_mc_run", dict(cn="nms", schedule="layered", tile=True), {}, False),
     "q6_flooding_lds": ("phys_mc_run", dict(NMS6), {}, False),
@@ -40,6 +41,8 @@ CASES = {
     "q6_layered_qtile": ("phys_mc_run", dict(NMS6, schedule="layered", qtile=True), {}, False),
     "spa_flooding_hbm_stats": ("phys_mc_run", dict(hbm=True), {}, True),
     "q6_flooding_qtile_stats": ("phys_mc_run", dict(NMS6, qtile=True), {}, True),
+    "nms_layered_tile_stats": ("phys_mc_run", dict(cn="nms", schedule="layered", tile=True), {}, True),
+    "q6_layered_qtile_stats": ("phys_mc_run", dict(NMS6, schedule="layered", qtile=True), {}, True),
     "bitflip_sliced": ("bitflip_mc_run", {}, {}, False),
     "bitflip_generic": ("bitflip_mc_run", dict(generic=True), {}, False),
 }

@@ -67,9 +67,10 @@ def _graph(H):
 @pytest.mark.parametrize("name,snr,B", [("wimax_576_0.5", -2.5, 192), ("wimax_2304_0.5", -2.5, 96),
                                          ("wimax_2304_0.75A", -1.0, 96), ("wimax_576_0.5", 0.0, 192)])
 def test_hbm_path_bit_identical_to_lds(gpu_available, name, snr, B):
-    """The 0 dB case pins the HBM path's early syndrome (phys_tile_syn_kernel /
-    phys_tile_exit_kernel after VN(1) and VN(2): conv = it, iters = it + 1) to
-    the LDS kernel frame by frame."""
+    """The 0 dB case pins the HBM path's early syndrome (phys_tile.hip's
+    phys_tile_syn_kernel, then phys_tile_state.hip's phys_tile_exit_kernel, the
+    exit both tile families share, after VN(1) and VN(2): conv = it, iters =
+    it + 1) to the LDS kernel frame by frame."""
     from ldpc_amd.device import phys_decode
     edd = ldpc_amd.load_committed_code(name)
     Hp = edd.physical_matrix()

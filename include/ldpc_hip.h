@@ -730,6 +730,66 @@ int ldpc_fading_get(const ldpc_decoder *d, int32_t *block_len);
 int ldpc_harq_set(ldpc_decoder *d, int32_t n_tx, const int32_t *tx_len, const int32_t *cols);
 int ldpc_harq_get(const ldpc_decoder *d, int32_t *n_tx, int32_t *tx_len_out, int32_t *cols_out, int32_t cols_cap);
 
+/* --------------------------------------- constellations (physical mode only)
+ * The channel models' modulations are square Gray QAM, demapped one axis at a
+ * time.  A decoder can instead carry a table of 2^bps complex points, 1 <= bps
+ * <= LDPC_CONST_MAX_BPS: PSK, APSK, cross or rotated QAM, any labelling (new
+ * symbols under ABI 5: an addition only, the version stays 5).  It is set as
+ * the channel, the pattern, the interleaver and the plan are and is independent
+ * of them.  points holds 2^bps pairs (re, im), indexed by label.  No decoder
+ * kernel knows of it; it only changes the frames of ldpc_generate_frames,
+ * ldpc_phys_mc_run, _ex, _q and ldpc_bf_mc_run.
+ * While a table is set and the channel model is LDPC_CH_AWGN or
+ * LDPC_CH_RAYLEIGH, the table replaces the channel's modulation: the bits per
+ * symbol and the mapping.  ldpc_channel_set / ldpc_channel_get are untouched
+ * and keep reporting what was set.  Everything the channel-model, rate-matching,
+ * interleaver, block-fading and HARQ contracts say of "symbol s" and
+ * "transmitted position t" holds with the table's bps: symbol s carries the
+ * positions s*bps .. s*bps + bps - 1.  This also holds for bps = 1: a one-bit
+ * table is a complex symbol with a noise pair of its own, it does not follow
+ * the built-in BPSK's two-bits-per-pair rule.
+ * Label: a = sum_t bit(s*bps + t) << (bps - 1 - t), the first bit the most
+ * significant; the point sent is x = points[a].
+ * Draws: the noise of symbol s is the N(0,1) pair of counter word s, g[0] on I
+ * and g[1] on Q; under LDPC_CH_RAYLEIGH there is one real fade h per symbol, of
+ * index s, or floor(s / block_len) under ldpc_fading_set, drawn exactly as for a
+ * QAM symbol.  The info bits and the parities are unchanged.
+ * Received value and LLRs, all fp64: r = h x + sigma (g0 + i g1); over all 2^bps
+ * points mu_i = ((r_I - h x_i,I)^2 + (r_Q - h x_i,Q)^2) / (2 sigma^2);
+ *   exact    llr_t = LSE_{a_t(i)=1}(-mu_i) - LSE_{a_t(i)=0}(-mu_i), each
+ *            log-sum-exp with its own maximum taken out first (finite for every
+ *            finite input);
+ *   max-log  llr_t = min_{a_t=0} mu_i - min_{a_t=1} mu_i.
+ * There is no one-bit-per-axis special case: a table that spells out QPSK goes
+ * through the same expressions, and gives the built-in QPSK's frames to within
+ * rounding, not bit for bit.  sigma keeps its meaning, Es/N0 = 1 / (2 sigma^2);
+ * for that to hold the table must have unit mean energy.
+ * The library ships no standard's table.  The built-in names of the Python
+ * layer (ldpc_amd.Constellation.psk8, .apsk16) are this project's own
+ * labellings, written out in its documentation; they claim no conformity with
+ * any standard, whose table a user loads from a file.
+ * ldpc_constellation_set validates, copies the table into the decoder's host
+ * memory and does no device work; bps == 0 (points may be NULL) clears the
+ * table.  The kernels of the first run that needs it get it as an argument; no
+ * device memory is held for it.  It is LDPC_EINVAL, and the earlier table stays
+ * in force, for: a NULL decoder; bps < 0 or bps > LDPC_CONST_MAX_BPS; NULL
+ * points with bps > 0; a coordinate that is not finite; |mean |x|^2 - 1| > 1e-9;
+ * two points equal in both coordinates.
+ * LDPC_EINVAL when frames are to be generated, before any device work, with a
+ * message that names the setting and how to clear it: a table under the
+ * reference channel; a table with LDPC_F_TEST_ZERO; n, E or any E_r not
+ * divisible by the table's bps (this replaces the check against the channel's
+ * modulation).  The parity-mode ldpc_mc_run and ldpc_frame_order are
+ * LDPC_EINVAL while a table is set.
+ * ldpc_constellation_get writes *bps (0: no table); points_out == NULL only
+ * asks for that, else cap, counted in doubles, must hold 2 * 2^bps values
+ * (LDPC_EINVAL if too small).  A failed-frame record of ldpc_mc_stats_read
+ * still regenerates with ldpc_generate_frames on the same decoder.  The
+ * generated frames equal a numpy restatement (tests/constellation_ref.py). */
+#define LDPC_CONST_MAX_BPS 6
+int ldpc_constellation_set(ldpc_decoder *d, int32_t bps, const double *points);
+int ldpc_constellation_get(const ldpc_decoder *d, int32_t *bps, double *points_out, int32_t cap);
+
 /* ------------------------------------------------ multi-GPU (RCCL, xGMI)
  * One process per GPU; frames are sharded by global index, so the only
  * exchange is ONE all-reduce of the int64 counter matrix per Monte-Carlo step

@@ -38,6 +38,8 @@
 // A bit interleaver (ldpc_interleaver_set) is those kernels with a permuted
 // tx_col; alone it has nothing to fill.  Rayleigh with a coherence length
 // (ldpc_fading_set) is frame_model_bf_kernel / frame_model_bf_row_kernel.
+// Under a constellation table (ldpc_constellation_set, ch.table) none of these
+// runs: the launchers at the end hand over to frame_constellation.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -469,6 +471,8 @@ hipError_t launch_frame_channel_model(const DevGraph &g, const DevState &st, con
                                       const FrameChannel &ch, hipStream_t s) {
     if (ch.bps < 1 || g.n % ch.bps != 0 || st.count <= 0) return hipErrorInvalidValue;
     if (ch.fade_block < 1 || (ch.fade_block > 1 && ch.model != kChRayleigh)) return hipErrorInvalidValue;
+    if (ch.table)  // a constellation table: frame_constellation.hip
+        return launch_frame_table(g, st, pt, seed, snr_point, sigma, frame0, out, row_out, ch, nullptr, g.n, nullptr, s);
     if (ch.fade_block > 1)
         return launch_model_bf_of<false>(g, st, pt, RateMatchDev{}, seed, snr_point, sigma, frame0, out, row_out, ch, s);
     if (ch.model == kChRayleigh)
@@ -487,6 +491,11 @@ hipError_t launch_frame_channel_model_rm(const DevGraph &g, const DevState &st, 
         (rm.n_fill > 0 && (!rm.fill_col || !rm.fill_llr)))
         return hipErrorInvalidValue;
     if (ch.fade_block < 1 || (ch.fade_block > 1 && ch.model != kChRayleigh)) return hipErrorInvalidValue;
+    if (ch.table) {  // a constellation table: frame_constellation.hip
+        const hipError_t e =
+            launch_frame_table(g, st, pt, seed, snr_point, sigma, frame0, out, row_out, ch, rm.tx_col, rm.E, nullptr, s);
+        return e != hipSuccess ? e : launch_fill(g, st, pt, rm, out, row_out, s);
+    }
     if (ch.fade_block > 1)
         return launch_model_bf_of<true>(g, st, pt, rm, seed, snr_point, sigma, frame0, out, row_out, ch, s);
     if (ch.model == kChRayleigh)

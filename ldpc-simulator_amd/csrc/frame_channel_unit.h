@@ -152,5 +152,136 @@ __device__ __forceinline__ void block_fades(uint64_t seed, int64_t F, int snr_po
     }
 }
 
+// ------------------------------------------------------ constellation table
+// The second unit kind (include/ldpc_hip.h "constellations"): one symbol of a
+// table of 2^BPS complex points, for every BPS one noise pair of its own.
+// The table travels as a kernel argument, so the loops over its points, which
+// are uniform across the wavefront in both kernel forms, read it with scalar
+// loads; every array below has static indices after unrolling.
+template <int BPS>
+struct TablePoints {
+    double xy[2 << BPS];  // re, im of label 0, 1, ...
+};
+
+template <int BPS>
+struct TableUnit {
+    static constexpr int kPoints = 1 << BPS;
+    static constexpr int kPerBlock = 128 / BPS;  // symbols a block of the tile form walks
+};
+
+// At most this far below the nearest point's class does the other class of a
+// bit share the nearest point's exponentials; exp(-500) is still a normal number.
+constexpr double kTableShareMax = 500.0;
+
+// llr[0 .. BPS) of the symbol with label a, fade h and noise g: r = h x_a +
+// sigma g, mu_i = |r - h x_i|^2 / (2 sigma^2).
+// Exact: e_i = exp(-(mu_i - m)) with m the smallest mu, once per point.  The
+// class of bit t that holds the nearest point has its own maximum m, so its
+// sum is the contract's.  The other class (smallest metric m') takes the same
+// e_i while m' - m <= kTableShareMax: log(sum e_i) - m is its LSE with a
+// relative error of (m' - m) 2^-53 in each term; beyond that it takes its own
+// exp(-(mu_i - m')).  2^BPS exponentials a symbol, plus 2^BPS (half of them of
+// -inf) for each bit whose classes are more than kTableShareMax apart.
+template <int BPS, int DEMAP>
+__device__ __forceinline__ void table_llr(const TablePoints<BPS> &tab, uint32_t a, double h, double sigma,
+                                          const double g[2], double *llr) {
+    constexpr int P = 1 << BPS;
+    double xr = 0.0, xq = 0.0;  // the one per-lane lookup, as selects over the uniform loop
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+        xr = a == (uint32_t)i ? tab.xy[2 * i] : xr;
+        xq = a == (uint32_t)i ? tab.xy[2 * i + 1] : xq;
+    }
+    const double rr = h * xr + sigma * g[0];
+    const double rq = h * xq + sigma * g[1];
+    const double two_s2 = 2.0 * (sigma * sigma);
+    double mu[P];
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+        const double dr = rr - h * tab.xy[2 * i];
+        const double dq = rq - h * tab.xy[2 * i + 1];
+        mu[i] = (dr * dr + dq * dq) / two_s2;
+    }
+    if constexpr (DEMAP == kDemapMaxlog) {
+#pragma unroll
+        for (int t = 0; t < BPS; ++t) {
+            double mn[2] = {INFINITY, INFINITY};
+#pragma unroll
+            for (int i = 0; i < P; ++i) mn[(i >> (BPS - 1 - t)) & 1] = fmin(mn[(i >> (BPS - 1 - t)) & 1], mu[i]);
+            llr[t] = mn[0] - mn[1];
+        }
+    } else {
+        double m = mu[0];
+#pragma unroll
+        for (int i = 1; i < P; ++i) m = fmin(m, mu[i]);
+        double e[P];
+#pragma unroll
+        for (int i = 0; i < P; ++i) e[i] = exp(-(mu[i] - m));
+        // the near path of every bit with static class tests: one fmin and one
+        // add per point and bit
+        uint32_t far_bits = 0u;
+#pragma unroll
+        for (int t = 0; t < BPS; ++t) {
+            double mn[2] = {INFINITY, INFINITY}, s[2] = {0.0, 0.0};
+#pragma unroll
+            for (int i = 0; i < P; ++i) {
+                const int c = (i >> (BPS - 1 - t)) & 1;
+                mn[c] = fmin(mn[c], mu[i]);
+                s[c] += e[i];
+            }
+            llr[t] = (log(s[1]) - m) - (log(s[0]) - m);
+            if (fmax(mn[0], mn[1]) - m > kTableShareMax) far_bits |= 1u << t;
+        }
+        // the far path: t is a run-time value here, so that the kernel holds
+        // its exponentials once, not once per bit; mu and llr keep their
+        // static indices (the class tests become selects)
+        if (far_bits != 0u) {
+#pragma unroll 1
+            for (int t = 0; t < BPS; ++t) {
+                if (!((far_bits >> t) & 1u)) continue;
+                const int sh = BPS - 1 - t;
+                double mn0 = INFINITY, mn1 = INFINITY, s0 = 0.0, s1 = 0.0;
+#pragma unroll
+                for (int i = 0; i < P; ++i) {
+                    const bool one = (i >> sh) & 1;
+                    mn0 = one ? mn0 : fmin(mn0, mu[i]);
+                    mn1 = one ? fmin(mn1, mu[i]) : mn1;
+                    s0 += one ? 0.0 : e[i];
+                    s1 += one ? e[i] : 0.0;
+                }
+                // the class that does not hold the nearest point, and its smallest metric
+                const bool far1 = mn1 > mn0;
+                const double mo = far1 ? mn1 : mn0;
+                double so = 0.0;
+#pragma unroll
+                for (int i = 0; i < P; ++i) {
+                    const bool one = (i >> sh) & 1;
+                    // a point of the near class has no weight: exp(-inf) = +0
+                    so += exp(-(one == far1 ? mu[i] - mo : INFINITY));
+                }
+                const double lse_far = log(so) - mo;
+                const double lse_near = log(far1 ? s0 : s1) - m;
+                const double v = far1 ? lse_far - lse_near : lse_near - lse_far;
+#pragma unroll
+                for (int tt = 0; tt < BPS; ++tt) llr[tt] = tt == t ? v : llr[tt];
+            }
+        }
+    }
+}
+
+// The label of symbol i of frame F's transmitted sequence (first bit most
+// significant); position t is column tx[t], or column t without tx.
+template <int BPS>
+__device__ __forceinline__ uint32_t table_label(const uint32_t *Ut, const uint32_t *Pt, const uint32_t *Wt, int k, int i,
+                                                const int32_t *__restrict__ tx) {
+    uint32_t a = 0u;
+#pragma unroll
+    for (int t = 0; t < BPS; ++t) {
+        const int tb = i * BPS + t;
+        a = (a << 1) | frame_bit(Ut, Pt, Wt, k, tx ? tx[tb] : tb);
+    }
+    return a;
+}
+
 }  // namespace
 }  // namespace ldpc

@@ -188,7 +188,11 @@ hipError_t launch_frame_harq(const DevGraph &g, const DevState &st, const PhysTi
     if (ch.fade_block < 1 || (ch.fade_block > 1 && ch.model != kChRayleigh)) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(hq.acc, 0, sizeof(double) * (size_t)st.ntiles * g.n * kTile, s);  // +0.0
     if (e != hipSuccess) return e;
-    if (ch.fade_block > 1)
+    if (ch.table) {  // a constellation table: frame_constellation.hip's tile form adds into acc
+        for (int r = 0; r < hq.n_tx && e == hipSuccess; ++r)
+            e = launch_frame_table(g, st, pt, seed + (uint64_t)r * kHarqSeedStep, snr_point, sigma, frame0, out, row_out,
+                                   ch, hq.cols + hq.tx_off[r], hq.tx_len[r], hq.acc, s);
+    } else if (ch.fade_block > 1)
         e = launch_harq_acc_of<kChRayleigh, true>(g, st, pt, hq, seed, snr_point, sigma, frame0, ch, s);
     else if (ch.model == kChRayleigh)
         e = launch_harq_acc_of<kChRayleigh, false>(g, st, pt, hq, seed, snr_point, sigma, frame0, ch, s);

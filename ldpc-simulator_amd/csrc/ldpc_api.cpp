@@ -20,6 +20,7 @@
 
 #include "ldpc_internal.h"
 #include "mc_stats_host.h"
+#include "constellation_host.h"
 #include "rate_match_host.h"
 #include "spa_device.h"
 
@@ -139,6 +140,9 @@ struct ldpc_decoder {
     int32_t *hq_dev = nullptr;  // LDPC_HARQ_MAX_TX x n column entries, allocated once
     bool hq_stale = false;      // the plan changed since hq_dev was written
     double *hq_acc = nullptr;
+    // the frame source's constellation table (ldpc_constellation_set), on the host only: the kernels get it
+    // as an argument; bps == 0: none
+    ldpc::ConstellationTable ctab;
     // profiling (ldpc_profile_*)
     bool prof = false;
     struct Span {
@@ -338,6 +342,39 @@ DevGraph call_graph(const ldpc_decoder *d, uint32_t flags) {
     return G;
 }
 
+// The channel as the frame source's launchers take it: under a constellation
+// table (ldpc_constellation_set) bps is the table's and table points at it.
+ldpc::FrameChannel frame_channel(const ldpc_decoder *d) {
+    ldpc::FrameChannel c = d->chan;
+    if (d->ctab.bps > 0) {
+        c.bps = d->ctab.bps;
+        c.table = d->ctab.xy.data();
+    }
+    return c;
+}
+
+// The bits per symbol that n, E and every E_r must divide into, and whose they are.
+int frames_bps(const ldpc_decoder *d) { return d->ctab.bps > 0 ? d->ctab.bps : d->chan.bps; }
+const char *frames_bps_of(const ldpc_decoder *d) {
+    return d->ctab.bps > 0 ? "the constellation table's bits per symbol; ldpc_constellation_set(d, 0, NULL) clears the table"
+                           : "the channel's bits per symbol";
+}
+
+// A constellation table replaces the modulation of a channel model: it has
+// nothing to replace under the reference channel or its test erasures.
+int constellation_frames_check(const char *fn, const ldpc_decoder *d, uint32_t flags) {
+    if (d->ctab.bps == 0) return LDPC_OK;
+    const char *clear = "ldpc_constellation_set(d, 0, NULL) clears the table";
+    if (d->chan.model == LDPC_CH_REFERENCE)
+        return ldpc_fail(LDPC_EINVAL, "%s: a constellation table (ldpc_constellation_set, bps = %d) needs LDPC_CH_AWGN or "
+                                      "LDPC_CH_RAYLEIGH, this decoder has the reference channel (ldpc_channel_set; %s)",
+                         fn, d->ctab.bps, clear);
+    if (flags & LDPC_F_TEST_ZERO)
+        return ldpc_fail(LDPC_EINVAL, "%s: LDPC_F_TEST_ZERO (test erasures) needs the reference channel, this decoder "
+                                      "has a constellation table (ldpc_constellation_set; %s)", fn, clear);
+    return LDPC_OK;
+}
+
 // The same under a HARQ plan (ldpc_harq_set): the plan says what is sent, so
 // its own lengths divide into symbols and nothing else may say what is sent.
 int harq_frames_check(const char *fn, const ldpc_decoder *d, uint32_t flags) {
@@ -366,10 +403,10 @@ int harq_frames_check(const char *fn, const ldpc_decoder *d, uint32_t flags) {
                                       "decoder's channel model is %d (ldpc_fading_set(d, 1) clears it)", fn,
                          d->chan.fade_block, d->chan.model);
     for (size_t r = 0; r < d->hq_len.size(); ++r)
-        if (d->hq_len[r] % d->chan.bps != 0)
+        if (d->hq_len[r] % frames_bps(d) != 0)
             return ldpc_fail(LDPC_EINVAL, "%s: transmission %d of the HARQ plan (ldpc_harq_set) sends E_r = %d positions, "
-                                          "not a multiple of bps = %d (the channel's bits per symbol)", fn, (int)r,
-                             d->hq_len[r], d->chan.bps);
+                                          "not a multiple of bps = %d (%s)", fn, (int)r, d->hq_len[r], frames_bps(d),
+                             frames_bps_of(d));
     return LDPC_OK;
 }
 
@@ -377,6 +414,7 @@ int harq_frames_check(const char *fn, const ldpc_decoder *d, uint32_t flags) {
 // hold (no device work): the code length divides into symbols, and the
 // test-only erasures belong to the reference channel.
 int channel_frames_check(const char *fn, const ldpc_decoder *d, uint32_t flags) {
+    if (int rc = constellation_frames_check(fn, d, flags)) return rc;
     if (!d->hq_len.empty()) return harq_frames_check(fn, d, flags);
     const int n_fill = (int)(d->rm_punct.size() + d->rm_short.size());
     if (n_fill > 0 && d->chan.model == LDPC_CH_REFERENCE)
@@ -396,13 +434,13 @@ int channel_frames_check(const char *fn, const ldpc_decoder *d, uint32_t flags) 
                                       "decoder's channel model is %d (ldpc_fading_set(d, 1) clears it)", fn,
                          d->chan.fade_block, d->chan.model);
     if (d->chan.model == LDPC_CH_REFERENCE) return LDPC_OK;
-    if (n_fill > 0 && (n - n_fill) % d->chan.bps != 0)
+    if (n_fill > 0 && (n - n_fill) % frames_bps(d) != 0)
         return ldpc_fail(LDPC_EINVAL, "%s: E = %d transmitted bits (n = %d less %d punctured and %d shortened) is not a "
-                                      "multiple of bps = %d (the channel's bits per symbol)", fn, n - n_fill, n,
-                         (int)d->rm_punct.size(), (int)d->rm_short.size(), d->chan.bps);
-    if (n_fill == 0 && n % d->chan.bps != 0)
-        return ldpc_fail(LDPC_EINVAL, "%s: n = %d is not a multiple of bps = %d (the channel's bits per symbol)", fn, n,
-                         d->chan.bps);
+                                      "multiple of bps = %d (%s)", fn, n - n_fill, n, (int)d->rm_punct.size(),
+                         (int)d->rm_short.size(), frames_bps(d), frames_bps_of(d));
+    if (n_fill == 0 && n % frames_bps(d) != 0)
+        return ldpc_fail(LDPC_EINVAL, "%s: n = %d is not a multiple of bps = %d (%s)", fn, n, frames_bps(d),
+                         frames_bps_of(d));
     if (flags & LDPC_F_TEST_ZERO)
         return ldpc_fail(LDPC_EINVAL, "%s: LDPC_F_TEST_ZERO (test erasures) needs the reference channel, this decoder "
                                       "has a channel model set (ldpc_channel_set)", fn);
@@ -411,6 +449,9 @@ int channel_frames_check(const char *fn, const ldpc_decoder *d, uint32_t flags) 
 
 // The parity-mode entries reproduce the reference: its channel only.
 int channel_parity_check(const char *fn, const ldpc_decoder *d) {
+    if (d->ctab.bps > 0)
+        return ldpc_fail(LDPC_EINVAL, "%s: parity mode has the reference channel only; a constellation table is physical "
+                                      "mode's (ldpc_constellation_set(d, 0, NULL) clears the table)", fn);
     if (!d->hq_len.empty())
         return ldpc_fail(LDPC_EINVAL, "%s: parity mode sends every code once; a HARQ plan is physical mode's "
                                       "(ldpc_harq_set(d, 0, NULL, NULL) clears the plan)", fn);
@@ -1194,7 +1235,7 @@ int ldpc_generate_frames(ldpc_decoder *d, uint64_t seed, int32_t snr_point, doub
         return rc;
     }
     HIP_TRY(ldpc::launch_frames(G, d->st, phys_tile(d), seed, snr_point, sigma, frame0, ldpc::kFramesCh, nullptr,
-                                d->chan, s, rm, hq));
+                                frame_channel(d), s, rm, hq));
     // export writes u only for j<k, at [f][k]: give it the [count][k] buffer
     HIP_TRY(ldpc::launch_export_frames(G, d->st, u_dev, l_dev, s));
     if (!dev_ptrs) {
@@ -1989,7 +2030,7 @@ int phys_mc_drive(ldpc_decoder *d, uint64_t seed, int32_t n_points, const double
             float *rows = (float *)d->llr_stage;  // cap x n doubles: room for cap x n floats
             HIP_TRY(timed(d, LDPC_K_GEN, s, [&] {
                 return ldpc::launch_frames(G, st, phys_tile(d), seed, p, sigmas[p], frame0 + start, layout, rows,
-                                           d->chan, s, rm, hq);
+                                           frame_channel(d), s, rm, hq);
             }));
             if (tiles && ms.hist) HIP_TRY(ldpc::launch_mc_stats_slots(ms.slot_frame, ms.frame_base, cnt, s));
             if (int rc = chunk(st, cnt, rows, ctr, ms)) return rc;
@@ -2580,6 +2621,27 @@ int ldpc_harq_get(const ldpc_decoder *d, int32_t *n_tx, int32_t *tx_len_out, int
                              d->hq_cols.size());
         std::copy(d->hq_cols.begin(), d->hq_cols.end(), cols_out);
     }
+    return LDPC_OK;
+}
+
+// --------------------------------------------------------- constellations
+int ldpc_constellation_set(ldpc_decoder *d, int32_t bps, const double *points) {
+    const char *fn = "ldpc_constellation_set";
+    if (!d) return ldpc_fail(LDPC_EINVAL, "%s: NULL decoder", fn);
+    const std::string err = ldpc::constellation_validate(bps, points);
+    if (!err.empty()) return ldpc_fail(LDPC_EINVAL, "%s: %s", fn, err.c_str());
+    d->ctab.assign(bps, points);
+    return LDPC_OK;
+}
+
+int ldpc_constellation_get(const ldpc_decoder *d, int32_t *bps, double *points_out, int32_t cap) {
+    const char *fn = "ldpc_constellation_get";
+    if (!d) return ldpc_fail(LDPC_EINVAL, "%s: NULL decoder", fn);
+    if (!bps) return ldpc_fail(LDPC_EINVAL, "%s: NULL bps", fn);
+    *bps = d->ctab.bps;
+    if (const int need = d->ctab.copy_to(points_out, cap))
+        return ldpc_fail(LDPC_EINVAL, "%s: capacity %d is too small for the %d doubles of a table with bps = %d", fn, cap,
+                         need, d->ctab.bps);
     return LDPC_OK;
 }
 

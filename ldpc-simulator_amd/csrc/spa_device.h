@@ -313,6 +313,9 @@ struct FrameChannel {
     int bps = 1;
     int demap = 0;
     int fade_block = 1;  // Rayleigh: symbols (BPSK: bits) that share a fade (ldpc_fading_set); 1: a fade each
+    // a constellation table (ldpc_constellation_set; include/ldpc_hip.h "constellations"): 2 * 2^bps doubles in
+    // host memory, and bps is the table's; null: the channel's own modulation
+    const double *table = nullptr;
 };
 // A decoder's rate-matching pattern as the frame source's kernels read it
 // (include/ldpc_hip.h "rate matching"; tables built by rate_match_host.h, in
@@ -360,6 +363,12 @@ hipError_t launch_frame_channel_model(const DevGraph &g, const DevState &st, con
 hipError_t launch_frame_channel_model_rm(const DevGraph &g, const DevState &st, const PhysTile &pt, uint64_t seed,
                                          int snr_point, double sigma, int64_t frame0, FramesOut out, float *row_out,
                                          const FrameChannel &ch, const RateMatchDev &rm, hipStream_t s);
+// What the three above launch in place of their per-axis kernels under a constellation table
+// (frame_constellation.hip; ch.table set): the E positions of the column list tx (null: the n columns in
+// order) as the form `out`, or with acc (a HARQ transmission) added into it.
+hipError_t launch_frame_table(const DevGraph &g, const DevState &st, const PhysTile &pt, uint64_t seed, int snr_point,
+                              double sigma, int64_t frame0, FramesOut out, float *row_out, const FrameChannel &ch,
+                              const int32_t *tx, int E, double *acc, hipStream_t s);
 // st.ubits &= rm.umask, between the info words and the parity stage (rm.n_short > 0)
 hipError_t launch_frame_shorten(const DevGraph &g, const DevState &st, const RateMatchDev &rm, hipStream_t s);
 // convert: L = Lambda = -(float)ch (else the generator already wrote them)

@@ -12,7 +12,7 @@ from .code import (EncoderDecoderData, build_layers, build_standard_form, csr_fi
 from .enums import Result  # noqa: F401
 from .settings import Settings  # noqa: F401
 
-__all__ = ["EncoderDecoderData", "Settings", "Result", "SPA_Decoder", "Graph", "Decoder",
+__all__ = ["EncoderDecoderData", "Settings", "Result", "SPA_Decoder", "Graph", "Decoder", "Constellation",
            "build_standard_form", "build_layers", "csr_fingerprint", "load_committed_code", "device_count", "LdpcError"]
 
 
@@ -23,4 +23,7 @@ def __getattr__(name):  # lazy: the decoder classes touch the GPU only when used
     if name in ("Graph", "Decoder", "bitflip_decode"):
         from . import device
         return getattr(device, name)
+    if name == "Constellation":
+        from .constellation import Constellation
+        return Constellation
     raise AttributeError(name)

@@ -50,7 +50,7 @@ EXPORTED = (
     "ldpc_mc_stats_enable", "ldpc_mc_stats_read", "ldpc_channel_set", "ldpc_channel_get",
     "ldpc_rate_match_set", "ldpc_rate_match_get",
     "ldpc_interleaver_set", "ldpc_interleaver_get", "ldpc_fading_set", "ldpc_fading_get",
-    "ldpc_harq_set", "ldpc_harq_get",
+    "ldpc_harq_set", "ldpc_harq_get", "ldpc_constellation_set", "ldpc_constellation_get",
     "ldpc_phys_lds_bytes", "ldpc_phys_decode", "ldpc_phys_mc_run",
     "ldpc_phys_decode_ex", "ldpc_phys_mc_run_ex", "ldpc_phys_kernel_name_ex", "ldpc_layers_build",
     "ldpc_phys_decode_q", "ldpc_phys_mc_run_q", "ldpc_phys_kernel_name_q", "ldpc_phys_q_lds_bytes",
@@ -149,6 +149,8 @@ def _declare(lib):
         "ldpc_fading_get": (ctypes.c_int, [c_vp, P(c_i32)]),
         "ldpc_harq_set": (ctypes.c_int, [c_vp, c_i32, P(c_i32), P(c_i32)]),
         "ldpc_harq_get": (ctypes.c_int, [c_vp, P(c_i32), P(c_i32), P(c_i32), c_i32]),
+        "ldpc_constellation_set": (ctypes.c_int, [c_vp, c_i32, P(c_dbl)]),
+        "ldpc_constellation_get": (ctypes.c_int, [c_vp, P(c_i32), P(c_dbl), c_i32]),
         "ldpc_comm_unique_id": (ctypes.c_int, [c_vp]),
         "ldpc_comm_init": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, P(c_vp)]),
         "ldpc_comm_allreduce": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, c_u32, c_vp]),

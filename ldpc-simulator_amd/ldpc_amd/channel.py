@@ -70,13 +70,17 @@ def sigma_for_esn0(esn0_db):
     return math.sqrt(1.0 / (2.0 * 10.0 ** (float(esn0_db) / 10.0)))
 
 
-def sigma_for_ebn0(ebn0_db, rate, bps):
+def sigma_for_ebn0(ebn0_db, rate, bps, table=False):
     """The same at Eb/N0 (dB) for a code of rate `rate` on `bps` bits per symbol:
-    Es = rate * bps * Eb."""
+    Es = rate * bps * Eb.  bps is a built-in modulation's, or with table=True a
+    constellation table's (1 .. 6)."""
     rate, bps = float(rate), int(bps)
     if not 0.0 < rate <= 1.0:
         raise ValueError(f"rate must be in (0, 1], got {rate}")
-    if bps not in MODULATIONS.values():
+    if table:
+        if not 1 <= bps <= 6:
+            raise ValueError(f"a constellation table's bps must be in 1 .. 6, got {bps}")
+    elif bps not in MODULATIONS.values():
         raise ValueError(f"bps must be one of {sorted(MODULATIONS.values())}, got {bps}")
     return math.sqrt(1.0 / (2.0 * rate * bps * 10.0 ** (float(ebn0_db) / 10.0)))
 
@@ -105,9 +109,13 @@ def resolve_snr_axis(spec, snr_axis=None):
     return snr_axis
 
 
-def sigmas_for_axis(spec, snr_axis, snrs, rate, speed=1.0):
-    """sigma per SNR point under the axis (resolve_snr_axis has accepted it)."""
+def sigmas_for_axis(spec, snr_axis, snrs, rate, speed=1.0, constellation=None):
+    """sigma per SNR point under the axis (resolve_snr_axis has accepted it).
+    constellation (a constellation.Constellation): the Eb/N0 axis uses the
+    table's bits per symbol in place of the modulation's."""
     spec = spec or ChannelSpec()
+    if constellation is not None and snr_axis == "ebn0":
+        return [sigma_for_ebn0(s, rate, constellation.bps, table=True) for s in snrs]
     if snr_axis == "reference":
         return [1.0 / math.sqrt(2.0 * speed * (10.0 ** (s * 0.1))) for s in snrs]
     if snr_axis == "esn0":

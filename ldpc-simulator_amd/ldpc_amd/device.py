@@ -487,6 +487,38 @@ class Decoder:
         offs = np.concatenate([[0], np.cumsum(lens[:n.value])])
         return HarqPlan(tuple(tuple(int(x) for x in cols[offs[r]:offs[r + 1]]) for r in range(n.value)))
 
+    def set_constellation(self, c):
+        """The frame source's constellation table for generate(), phys_mc_run()
+        and bitflip_mc_run() on this decoder from now on
+        (ldpc_constellation_set): a constellation.Constellation, which replaces
+        the channel model's modulation while it is set; None clears it.  No
+        device work."""
+        from .constellation import Constellation
+        if c is None:
+            check("ldpc_constellation_set", _lib.lib().ldpc_constellation_set(self._h, 0, None))
+            self._constellation_name = "custom"
+            return
+        if not isinstance(c, Constellation):
+            raise ValueError(f"set_constellation takes a Constellation or None, got {type(c).__name__}")
+        xy = (ctypes.c_double * (2 * len(c.points)))(*c.flat())
+        check("ldpc_constellation_set", _lib.lib().ldpc_constellation_set(self._h, c.bps, xy))
+        self._constellation_name = c.name
+
+    @property
+    def constellation(self):
+        """The table in force as a constellation.Constellation (the library
+        stores the points; the name is the one last set here), None without one
+        (ldpc_constellation_get)."""
+        from .constellation import Constellation
+        bps = ctypes.c_int32(0)
+        check("ldpc_constellation_get", _lib.lib().ldpc_constellation_get(self._h, ctypes.byref(bps), None, 0))
+        if bps.value == 0:
+            return None
+        xy = (ctypes.c_double * (2 << bps.value))()
+        check("ldpc_constellation_get", _lib.lib().ldpc_constellation_get(self._h, ctypes.byref(bps), xy, len(xy)))
+        return Constellation(getattr(self, "_constellation_name", "custom"),
+                             tuple(complex(xy[2 * i], xy[2 * i + 1]) for i in range(1 << bps.value)))
+
     def generate(self, seed, snr_point, sigma, frame0, count, test_zero=False):
         """On-device synthetic frames (u bits, channel LLRs) copied back for testing.
         test_zero: the frame source's test-only erasures (LDPC_F_TEST_ZERO)."""

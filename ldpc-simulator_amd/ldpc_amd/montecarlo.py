@@ -222,7 +222,7 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
              rank=0, world=1, allreduce=None, matrix_path="", mode="parity", cn_rule="spa", schedule="flooding",
              alpha=0.75, beta=0.5, qbits=None, llr_scale=4.0, layered_tile=False, quant_tile=False, stats=False,
              max_failed=0, channel=None, snr_axis=None, rate_match=None, decoder="sumproduct", bf_weight=0.0,
-             bf_theta=0.0, interleaver=None, fading_block=1):
+             bf_theta=0.0, interleaver=None, fading_block=1, constellation=None):
     """Full sweep on this process's GPU -> SimulationResult (reference schema).
 
     mode "parity" is the reference's decoder on H_std; "physical" decodes the
@@ -264,10 +264,15 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
     known.  It needs mode="physical" and a channel model.  fading_block (an
     integer >= 1, or "frame") is the Rayleigh channel's coherence length in
     symbols (BPSK: bits): 1 is a fade per symbol, "frame" one fade per frame;
-    anything but 1 needs channel model "rayleigh"."""
+    anything but 1 needs channel model "rayleigh".
+    constellation (a constellation.Constellation; None = the channel's own
+    modulation) replaces the modulation by a table of 2^bps complex points: the
+    Eb/N0 axis and every divisibility check then use the table's bits per
+    symbol.  It needs mode="physical" and channel model "awgn" or "rayleigh"."""
     bf_weight, bf_theta = check_decoder_args(decoder, bf_weight, bf_theta, mode, cn_rule, schedule, qbits,
                                              layered_tile, quant_tile, nllr)
     bf = (bf_weight, bf_theta) if decoder == "bitflipping" else None
+    check_constellation_args(constellation, channel, mode)
     snr_axis = check_channel_args(channel, snr_axis, mode)
     rate_match = check_rate_match_args(rate_match, channel, mode)
     interleaver, fading_block = check_interleave_args(interleaver, fading_block, channel, mode)
@@ -294,7 +299,7 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
         return _simulate_graph(getattr(ira, IRA_CODES[matrix])(), matrix, t0, snrs, blocks, max_iter, seed, chunk,
                                device, rank, world, allreduce, matrix_path, cn_rule, schedule, alpha, beta, qbits,
                                llr_scale, layered_tile, quant_tile, stats, max_failed, channel, snr_axis, rate_match,
-                               bf, interleaver, fading_block)
+                               bf, interleaver, fading_block, constellation)
     if isinstance(matrix, EncoderDecoderData):
         edd = matrix
     elif isinstance(matrix, str) and os.path.exists(matrix):
@@ -305,10 +310,10 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
     rate, k_info = edd._rate, edd._k
     if channel is not None and not channel.is_reference:
         # ValueErrors before any device call
-        sent, k_info, rate = rate_match_shape(rate_match, channel, edd._n, edd._k)
-        channel.check_length(sent)
+        sent, k_info, rate = rate_match_shape(rate_match, channel, edd._n, edd._k, constellation)
+        (constellation or channel).check_length(sent)
         interleaver = resolve_interleaver(interleaver, sent)
-        sigmas = sigmas_for_axis(channel, snr_axis, snrs, rate)
+        sigmas = sigmas_for_axis(channel, snr_axis, snrs, rate, constellation=constellation)
     g = Graph(edd._h_std, device=device)
     dec = Decoder(g, Decoder.fit_slots(g, min(max(1, shard(int(blocks), rank, world)[1]), chunk)))
     if sigmas is not None:
@@ -316,6 +321,7 @@ def simulate(matrix, snrs, blocks, max_iter, seed=20260213, nllr=False, chunk=65
         dec.set_rate_match(rate_match)
         dec.set_interleaver(interleaver)
         dec.set_fading_block(fading_block)
+        dec.set_constellation(constellation)
     counter_fn = None
     if stats:
         dec.mc_stats(True, max_failed)
@@ -355,6 +361,22 @@ def check_channel_args(channel, snr_axis, mode):
         raise ValueError(f"the {channel.model} channel needs mode='physical' (the channel models are physical "
                          "mode's; parity mode reproduces the reference's channel)")
     return resolve_snr_axis(channel, snr_axis)
+
+
+def check_constellation_args(constellation, channel, mode):
+    """ValueError for a constellation table simulate() cannot honour (before any
+    code is loaded): it replaces the modulation of a channel model."""
+    from .constellation import Constellation
+    if constellation is None:
+        return None
+    if not isinstance(constellation, Constellation):
+        raise ValueError(f"constellation must be a Constellation or None, got {type(constellation).__name__}")
+    if mode != "physical":
+        raise ValueError("constellation needs mode='physical' (parity mode reproduces the reference's BPSK channel)")
+    if channel is None or channel.is_reference:
+        raise ValueError("constellation needs a channel model (channel=ChannelSpec('awgn' / 'rayleigh', ...)): the "
+                         "reference channel is BPSK only")
+    return constellation
 
 
 def check_rate_match_args(rate_match, channel, mode):
@@ -426,28 +448,35 @@ def interleave_header(info):
     return f"interleaver {what}  coherence length {fb}" + ("" if fb == "frame" else " symbol(s)")
 
 
-def rate_match_shape(rate_match, channel, n, k):
+def rate_match_shape(rate_match, channel, n, k, constellation=None):
     """(transmitted bits E, information bits, effective rate) of an (n, k) code
     under the pattern (None: n, k, k / n); ValueError for a pattern the code or
-    the channel's bits per symbol cannot carry."""
+    the bits per symbol (the constellation table's, else the channel's) cannot
+    carry."""
+    from .constellation import effective_bps
     if rate_match is None or rate_match.is_empty:
         return int(n), int(k), k / n
-    rate_match.validate(n, k, channel.bps)
+    rate_match.validate(n, k, effective_bps(channel, constellation))
     return rate_match.n_transmitted(n), rate_match.info_bits(k), rate_match.effective_rate(n, k)
 
 
-def channel_info(channel, snr_axis, snrs, rate, rate_match=None, n=None, k=None, interleaver=None, fading_block=1):
+def channel_info(channel, snr_axis, snrs, rate, rate_match=None, n=None, k=None, interleaver=None, fading_block=1,
+                 constellation=None):
     """The sweep's channel as --stats-json writes it: model, modulation, demap,
     snr_axis and sigma per point; under a rate-matching pattern (then with the
     mother code's n and k, and `rate` the effective rate) also "rate_match":
     the columns, the transmitted and information bits and the rate; with an
     interleaver (an Interleaver) "interleaver": its info(); with a coherence
-    length other than 1 "fading_block" (FADING_FRAME as "frame")."""
+    length other than 1 "fading_block" (FADING_FRAME as "frame"); under a
+    constellation table "constellation": its name, bps and points (sigma then
+    follows the table's bps, and "modulation" is what the table replaced)."""
     from .channel import ChannelSpec, resolve_snr_axis, sigmas_for_axis
     channel = channel or ChannelSpec()
     snr_axis = resolve_snr_axis(channel, snr_axis)
     info = {"model": channel.model, "modulation": channel.modulation, "demap": channel.demap, "snr_axis": snr_axis,
-            "sigma": [float(x) for x in sigmas_for_axis(channel, snr_axis, snrs, rate)]}
+            "sigma": [float(x) for x in sigmas_for_axis(channel, snr_axis, snrs, rate, constellation=constellation)]}
+    if constellation is not None:
+        info["constellation"] = constellation.info()
     if rate_match is not None and not rate_match.is_empty:
         info["rate_match"] = rate_match.info(n, k)
     if interleaver is not None:
@@ -472,7 +501,7 @@ def check_stats_args(stats, max_failed, mode, world):
 def _simulate_graph(H, name, t0, snrs, blocks, max_iter, seed, chunk, device, rank, world, allreduce, matrix_path,
                     cn_rule, schedule, alpha, beta, qbits, llr_scale, layered_tile, quant_tile=False, stats=False,
                     max_failed=0, channel=None, snr_axis="reference", rate_match=None, bf=None, interleaver=None,
-                    fading_block=1):
+                    fading_block=1, constellation=None):
     """simulate() in physical mode on an IRA graph H: one graph, the decoder's
     frame source and the graph it decodes on (as bench.py's config 5).
     bf: (weight, theta) of the bit-flipping decoder, None for the others."""
@@ -484,10 +513,10 @@ def _simulate_graph(H, name, t0, snrs, blocks, max_iter, seed, chunk, device, ra
     if channel is not None and not channel.is_reference:
         from .channel import sigmas_for_axis
         # ValueErrors before any device call
-        sent, k_info, rate = rate_match_shape(rate_match, channel, n, k)
-        channel.check_length(sent)
+        sent, k_info, rate = rate_match_shape(rate_match, channel, n, k, constellation)
+        (constellation or channel).check_length(sent)
         interleaver = resolve_interleaver(interleaver, sent)
-        sigmas = sigmas_for_axis(channel, snr_axis, snrs, rate)
+        sigmas = sigmas_for_axis(channel, snr_axis, snrs, rate, constellation=constellation)
     g = Graph(H, device=device)
     dec = Decoder(g, Decoder.fit_slots(g, min(max(1, shard(int(blocks), rank, world)[1]), chunk)))
     if sigmas is not None:
@@ -495,6 +524,7 @@ def _simulate_graph(H, name, t0, snrs, blocks, max_iter, seed, chunk, device, ra
         dec.set_rate_match(rate_match)
         dec.set_interleaver(interleaver)
         dec.set_fading_block(fading_block)
+        dec.set_constellation(constellation)
 
     def counter_fn(sigmas, cnt, frame0):
         if bf is not None:
@@ -581,7 +611,7 @@ def simulate_harq(matrix, snrs, blocks, max_iter, harq, seed=20260213, chunk=655
                   allreduce=None, mode="physical", cn_rule="spa", schedule="flooding", alpha=0.75, beta=0.5,
                   qbits=None, llr_scale=4.0, layered_tile=False, quant_tile=False, stats=False, max_failed=0,
                   channel=None, snr_axis=None, rate_match=None, decoder="sumproduct", bf_weight=0.0, bf_theta=0.0,
-                  interleaver=None, fading_block=1):
+                  interleaver=None, fading_block=1, constellation=None):
     """A physical-mode sweep under a HARQ plan (harq: a harq.HarqPlan, or one of
     its spec strings chase:R[:E], ir:R:E, file:PATH, resolved against the code
     and the pattern's shortened columns).  The keywords are simulate()'s
@@ -605,12 +635,14 @@ def simulate_harq(matrix, snrs, blocks, max_iter, harq, seed=20260213, chunk=655
                                              layered_tile, quant_tile, False)
     bf = (bf_weight, bf_theta) if decoder == "bitflipping" else None
     check_harq_args(harq, channel, mode, interleaver, rate_match)
+    check_constellation_args(constellation, channel, mode)
     snr_axis = check_channel_args(channel, snr_axis, mode)
     rate_match = check_rate_match_args(rate_match, channel, mode)
     _, fading_block = check_interleave_args(None, fading_block, channel, mode)
     from .channel import sigmas_for_axis
     from .code import EncoderDecoderData, load_committed_code
     from .device import Decoder, Graph, phys_flags, phys_quant_args, phys_rule_args
+    from .constellation import effective_bps
     from .harq import resolve as resolve_harq
     check_stats_args(stats, max_failed, mode, world)
     phys_rule_args(cn_rule, schedule, alpha, beta)
@@ -637,15 +669,17 @@ def simulate_harq(matrix, snrs, blocks, max_iter, harq, seed=20260213, chunk=655
     shortened = rate_match.shortened if rate_match is not None else ()
     if rate_match is not None:
         rate_match.validate(n, k)
-    plan = resolve_harq(harq, n, shortened).validate(n, shortened, channel.bps)
+    bps = effective_bps(channel, constellation)
+    plan = resolve_harq(harq, n, shortened).validate(n, shortened, bps)
     k_info = k - len(shortened)
-    sigmas = sigmas_for_axis(channel, snr_axis, snrs, k_info / plan.n_sent(0))
+    sigmas = sigmas_for_axis(channel, snr_axis, snrs, k_info / plan.n_sent(0), constellation=constellation)
     g = Graph(h_src, device=device)
     gp = g if h_phys is h_src else Graph(edd.physical_matrix(), device=device)
     dec = Decoder(g, Decoder.fit_slots(g, min(max(1, shard(int(blocks), rank, world)[1]), chunk)))
     dec.set_channel(channel)
     dec.set_rate_match(rate_match)
     dec.set_fading_block(fading_block)
+    dec.set_constellation(constellation)
     if stats:
         dec.mc_stats(True, max_failed)
 
@@ -667,8 +701,10 @@ def simulate_harq(matrix, snrs, blocks, max_iter, harq, seed=20260213, chunk=655
     pts = []
     for p, snr in enumerate(snrs):
         pts.append({"snr_db": float(snr), "frames": int(ctrs[0, p, 0]),
-                    **harq_point(ctrs[:, p], plan.lengths, k_info, channel.bps)})
+                    **harq_point(ctrs[:, p], plan.lengths, k_info, bps)})
     res = {"plan": plan.info(), "sigma": [float(x) for x in sigmas], "counters": ctrs, "points": pts}
+    if constellation is not None:
+        res["constellation"] = constellation.info()
     if stats:
         res["stats"] = sts
     return res
@@ -685,6 +721,8 @@ def harq_to_json(path, seed, res):
     import json
     doc = {"seed": int(seed), "plan": res["plan"], "sigma": res["sigma"], "points": res["points"],
            "counters": np.asarray(res["counters"]).tolist()}
+    if "constellation" in res:
+        doc["constellation"] = res["constellation"]
     with open(path, "w") as f:
         json.dump(doc, f, indent=1)
 
@@ -732,8 +770,13 @@ def build_parser():
                     help="with --stats-json: keep up to N failed-frame records per SNR point (default 0)")
     ap.add_argument("--channel", choices=("reference", "awgn", "rayleigh"), default="reference",
                     help="physical mode: a textbook channel model under the frames (default: the reference's channel)")
-    ap.add_argument("--modulation", choices=("bpsk", "qpsk", "qam16", "qam64"), default="bpsk",
-                    help="with --channel awgn / rayleigh: Gray-mapped square constellation")
+    ap.add_argument("--modulation", choices=("bpsk", "qpsk", "qam16", "qam64"), default=None,
+                    help="with --channel awgn / rayleigh: Gray-mapped square constellation (default bpsk)")
+    ap.add_argument("--constellation", default=None, metavar="SPEC",
+                    help="with --channel awgn / rayleigh, in place of --modulation: a table of 2^bps complex points, "
+                         "demapped over all of them: 8psk, 16apsk[:GAMMA] (ring ratio, default 3.15; both labellings "
+                         "are this project's own, see ldpc_amd/constellation.py) or file:PATH (one `re im` per line, "
+                         "the line index is the label, unit mean energy)")
     ap.add_argument("--demap", choices=("exact", "maxlog"), default="exact",
                     help="with --channel awgn / rayleigh: exact or max-log bit LLRs")
     ap.add_argument("--snr-axis", choices=("reference", "esn0", "ebn0"), default=None,
@@ -769,6 +812,12 @@ def parse_args(argv=None):
     from .device import phys_flags, phys_quant_args, phys_rule_args
     ap = build_parser()
     a = ap.parse_args(argv)
+    if a.constellation is not None:
+        if a.modulation is not None:
+            ap.error("--constellation replaces the modulation: it takes no --modulation")
+        if a.mode != "physical" or a.channel == "reference":
+            ap.error("--constellation needs --mode physical --channel awgn or rayleigh")
+    a.modulation = "bpsk" if a.modulation is None else a.modulation
     if a.channel == "reference" and (a.modulation != "bpsk" or a.demap != "exact"):
         ap.error("--modulation and --demap need --channel awgn or rayleigh")
     if a.mode != "physical" and (a.cn_rule != "spa" or a.schedule != "flooding" or a.alpha is not None
@@ -829,6 +878,11 @@ def parse_args(argv=None):
     a.beta = 0.5 if a.beta is None else a.beta
     try:
         a.channel_spec = ChannelSpec(a.channel, a.modulation, a.demap)
+        a.constellation_table = None
+        if a.constellation is not None:
+            from .constellation import parse as parse_constellation
+            a.constellation_table = check_constellation_args(parse_constellation(a.constellation), a.channel_spec,
+                                                             a.mode)
         a.snr_axis = check_channel_args(a.channel_spec, a.snr_axis, a.mode)
         a.interleaver, a.fading_block = check_interleave_args(a.interleaver, a.fading_block, a.channel_spec, a.mode)
         check_ira_mode(a.matrix, a.mode)
@@ -865,7 +919,8 @@ def cli_rate_match(a, shape=None):
     n, k = shape or code_shape(a.matrix)
     rm = RateMatch(parse_columns(a.puncture, n, k) if a.puncture is not None else (),
                    parse_columns(a.shorten, n, k) if a.shorten is not None else ())
-    return rm.validate(n, k, a.channel_spec.bps)
+    from .constellation import effective_bps
+    return rm.validate(n, k, effective_bps(a.channel_spec, a.constellation_table))
 
 
 def rate_match_header(rm_info, n, k):
@@ -875,23 +930,40 @@ def rate_match_header(rm_info, n, k):
             f"effective rate {rm_info['rate']:.6f}")
 
 
+def modulation_header(channel, constellation):
+    """The header line's modulation field: the table's name while one is set."""
+    return f"modulation {channel.modulation}" if constellation is None else f"constellation {constellation.name}"
+
+
+def constellation_header(constellation):
+    """The command line's header line of a sweep under a constellation table."""
+    return (f"constellation {constellation.name}  bps {constellation.bps}  {len(constellation.points)} points, "
+            "demapped over all of them")
+
+
 def main_harq(a, snrs, rate_match, rank, world, local, allreduce, comm):
     """main() under --harq: simulate_harq and its own report."""
+    from .constellation import effective_bps
     from .harq import resolve as resolve_harq
     try:  # resolved here, without a device, so that a bad plan ends before any device call
         n, k = code_shape(a.matrix)
         shortened = rate_match.shortened if rate_match is not None else ()
-        plan = resolve_harq(a.harq, n, shortened).validate(n, shortened, a.channel_spec.bps)
+        plan = resolve_harq(a.harq, n, shortened).validate(
+            n, shortened, effective_bps(a.channel_spec, a.constellation_table))
     except (ValueError, OSError) as e:
         raise SystemExit(f"--harq: {e}")
     res = simulate_harq(a.matrix, snrs, a.blocks, a.iterations, plan, seed=a.seed, device=local, rank=rank,
                         world=world, allreduce=allreduce, mode=a.mode, cn_rule=a.cn_rule, schedule=a.schedule,
                         alpha=a.alpha, beta=a.beta, qbits=a.qbits, llr_scale=a.llr_scale, layered_tile=a.layered_tile,
                         quant_tile=a.quant_tile, channel=a.channel_spec, snr_axis=a.snr_axis, rate_match=rate_match,
-                        decoder=a.decoder, bf_weight=a.bf_weight, bf_theta=a.bf_theta, fading_block=a.fading_block)
+                        decoder=a.decoder, bf_weight=a.bf_weight, bf_theta=a.bf_theta, fading_block=a.fading_block,
+                        constellation=a.constellation_table)
     if rank == 0:
-        print(f"channel {a.channel_spec.model}  modulation {a.channel_spec.modulation}  demap {a.channel_spec.demap}  "
+        print(f"channel {a.channel_spec.model}  {modulation_header(a.channel_spec, a.constellation_table)}  "
+              f"demap {a.channel_spec.demap}  "
               f"SNR axis {a.snr_axis}  sigma " + " ".join(f"{x:.6f}" for x in res["sigma"]))
+        if a.constellation_table is not None:
+            print(constellation_header(a.constellation_table))
         print(harq_header(res["plan"]))
         for pt in res["points"]:
             print(f"SNR {pt['snr_db']:.2f} dB  FER after r " + " ".join(f"{x:.6f}" for x in pt["fer_after"])
@@ -925,7 +997,8 @@ def main(argv=None):
     if interleaver is not None:
         try:  # resolved here, without a device, so that the header and the JSON name what ran
             n, k = code_shape(a.matrix)
-            interleaver = resolve_interleaver(interleaver, rate_match_shape(rate_match, a.channel_spec, n, k)[0])
+            interleaver = resolve_interleaver(
+                interleaver, rate_match_shape(rate_match, a.channel_spec, n, k, a.constellation_table)[0])
         except (ValueError, OSError) as e:
             raise SystemExit(f"--interleaver: {e}")
     out = simulate(a.matrix, snrs, a.blocks, a.iterations, seed=a.seed, nllr=a.normalized_llr,
@@ -934,15 +1007,18 @@ def main(argv=None):
                    layered_tile=a.layered_tile, quant_tile=a.quant_tile, stats=a.stats_json is not None,
                    max_failed=a.max_failed, channel=a.channel_spec, snr_axis=a.snr_axis, rate_match=rate_match,
                    decoder=a.decoder, bf_weight=a.bf_weight, bf_theta=a.bf_theta, interleaver=interleaver,
-                   fading_block=a.fading_block)
+                   fading_block=a.fading_block, constellation=a.constellation_table)
     res = out[0]
     info = channel_info(a.channel_spec, a.snr_axis, snrs, res.config.rate, rate_match, res.config.n, res.config.k,
-                        interleaver, a.fading_block)
+                        interleaver, a.fading_block, a.constellation_table)
     if rank == 0 and a.stats_json is not None:
         stats_to_json(a.stats_json, a.seed, out[2], channel=info)
     if rank == 0:
-        print(f"channel {info['model']}  modulation {info['modulation']}  demap {info['demap']}  "
+        print(f"channel {info['model']}  {modulation_header(a.channel_spec, a.constellation_table)}  "
+              f"demap {info['demap']}  "
               f"SNR axis {info['snr_axis']}  sigma " + " ".join(f"{x:.6f}" for x in info["sigma"]))
+        if a.constellation_table is not None:
+            print(constellation_header(a.constellation_table))
         if "rate_match" in info:
             print(rate_match_header(info["rate_match"], res.config.n, res.config.k))
         if "interleaver" in info or "fading_block" in info:
